@@ -5,15 +5,19 @@ Metric (BASELINE.json): centroidal QPs/sec (N=10, 13-state/12-input) at batch=40
 One "step" = one cmpc_solve_batch over a batch of synthetic QPs already resident in HBM: SRBD linearisation +
 condensing + pyramid stacking + batched IPM + scatter/rollout (the whole hot path, nothing skipped).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N      (one process per GPU)
 
 Multi-GPU: the QP batch shards with no data-path collective (weak scaling, B per GPU, QP ids offset by rank so every
 QP's inputs are the same whatever the sharding); gloo is used only for the start/stop barriers and the max-over-ranks
 time. Rank 0 prints one JSON line. `bench.py --gpus N` (N > 1) without a launcher starts its N ranks itself, one
-child process per GPU, before anything touches the GPU. `value` is the solve throughput; `value_end_to_end` repeats the
-timed steps with every step's U shard copied into rank 0's GPU (the xGMI result gather of SURVEY section 8e) inside the
-timed window.
+child process per GPU, before anything touches the GPU. `value` is the solve throughput.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given and
+prints the line. --full adds every other measurement and check: `value_short_warmup`, `value_end_to_end` (the timed
+steps repeated with every step's U shard copied into rank 0's GPU, the xGMI result gather of SURVEY section 8e, inside
+the timed window), the CPU baselines and the comparison with the fp64 CPU oracle; with --ocp the B = 1 latencies, the
+C++ mirror's tick and the CPU oracle.
 """
 import argparse
 import json
@@ -128,41 +132,19 @@ def ocp_main(args):
     H.hipEventElapsedTime(C.byref(ms_ev), ev[0], ev[1])
     kernel_ms = ms_ev.value / args.steps  # one k_ocp_ipm launch per step on this stream
     st, it = dst.host(), dit.host()
-    # B = 1: the latency of one HpipmInterface::solve on the device (kernel only, then with the host copies)
-    reps = 50
-    H.hipEventRecord(ev[0], stream)
-    for _ in range(reps):
-        solve(1)
-    H.hipEventRecord(ev[1], stream)
-    H.hipStreamSynchronize(stream)
-    H.hipEventElapsedTime(C.byref(ms_ev), ev[0], ev[1])
-    ms_b1 = ms_ev.value / reps
-    t = time.perf_counter()
-    for _ in range(10):
-        solver.solve(x0[:1], recs[:1], crecs[:1] if crecs is not None else None)
-    ms_b1_host_copy = (time.perf_counter() - t) / 10 * 1e3
-    # the host path as the C++ mirror drives it: the problem written into the handle's pinned staging (no host copy),
-    # cmpc_ocp_solve_host (one H2D of the records, the kernel, one D2H of x / u)
-    ms_b1_host = None
-    stg = solver.staging() if B == 1 else None
-    if stg is not None:
-        sx0, srec, screc = stg
-        sx0[0] = x0[0]
-        srec[0] = recs[0]
-        if screc is not None:
-            screc[0] = crecs[0]
-        solver.solve(sx0[:1], srec[:1], screc[:1] if screc is not None else None)
-        t = time.perf_counter()
-        for _ in range(20):
-            solver.solve(sx0[:1], srec[:1], screc[:1] if screc is not None else None)
-        ms_b1_host = (time.perf_counter() - t) / 20 * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank,
+                     {"x": dx.host(), "u": du.host()[:, :solver.nU], "status": st, "iters": it})
+    ms_b1 = ms_b1_host = ms_b1_host_copy = None
+    if args.full:
+        ms_b1, ms_b1_host, ms_b1_host_copy = ocp_b1_latency(H, ev, stream, solve, solver, B, x0, recs, crecs)
     ok = st == 0
     iters_mean = float(it[ok].mean()) if ok.any() else 0.0
     flops = sum(ocp_flops(p0["nu"], p0.get("nc"), p0["nx"], float(it[b])) for b in range(B) if ok[b])
     ach = flops / (kernel_ms * 1e-3)
     okey = f"ocp_{args.ocp}_B{B}"
     traffic, traffic_src = pmc_traffic(os.path.join(ROOT, "profiles", f"traffic_{okey}.json"), "k_ocp")
-    tick = ocp_tick(gen, projected) if rank == 0 and not args.no_tick else None
+    tick = ocp_tick(gen, projected) if args.full and rank == 0 and not args.no_tick else None
     sq, sq_src = pmc_sq(okey, "k_ocp")
     sq_line = {"source": sq_src}
     if sq:
@@ -181,7 +163,7 @@ def ocp_main(args):
         "metric": f"HpipmInterface OCP-QP solves/sec (ocs2_legged_robot size: {shape}) at batch={B}",
         "value": value, "unit": "solves/s", "n_gpus": n_dev, "n_ranks": world, "shared_gpu": n_dev < world,
         "devices": dev_ids, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "full": args.full,
         "data": "synthetic (cheeta_mpc/ocp.py legged_problem, 16 seeded problems tiled over the batch)",
         "config": {"workload": f"{B} OCP-QPs per GPU, {shape}, stage-wise interior-point (HPIPM's method), fp64",
                    "batch_per_gpu": B, "parallelism": f"shard{world}"},
@@ -200,7 +182,7 @@ def ocp_main(args):
         "solver": {"success_frac": float(ok.mean()), "mean_iters": iters_mean},
         "build": {"version": cm.lib().cmpc_version().decode(), "lib_md5": lib_md5()},
     }
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_py as op  # test infrastructure: the CPU restatement, timed as the baseline
         op.select_build(oracle_fast_build()[0])
@@ -239,6 +221,59 @@ def ocp_main(args):
     if rank == 0:
         print(json.dumps(result), flush=True)
     dist.close()
+
+
+def ocp_b1_latency(H, ev, stream, solve, solver, B, x0, recs, crecs):
+    """--full, --ocp: the latency of one HpipmInterface::solve on the device at B = 1 (kernel only, then with the
+    host copies). Returns (ms kernel only, ms host path from the pinned staging or None, ms from numpy arrays)."""
+    import ctypes as C
+    ms_ev = C.c_float()
+    reps = 50
+    H.hipEventRecord(ev[0], stream)
+    for _ in range(reps):
+        solve(1)
+    H.hipEventRecord(ev[1], stream)
+    H.hipStreamSynchronize(stream)
+    H.hipEventElapsedTime(C.byref(ms_ev), ev[0], ev[1])
+    ms_b1 = ms_ev.value / reps
+    t = time.perf_counter()
+    for _ in range(10):
+        solver.solve(x0[:1], recs[:1], crecs[:1] if crecs is not None else None)
+    ms_b1_host_copy = (time.perf_counter() - t) / 10 * 1e3
+    # the host path as the C++ mirror drives it: the problem written into the handle's pinned staging (no host copy),
+    # cmpc_ocp_solve_host (one H2D of the records, the kernel, one D2H of x / u)
+    ms_b1_host = None
+    stg = solver.staging() if B == 1 else None
+    if stg is not None:
+        sx0, srec, screc = stg
+        sx0[0] = x0[0]
+        srec[0] = recs[0]
+        if screc is not None:
+            screc[0] = crecs[0]
+        solver.solve(sx0[:1], srec[:1], screc[:1] if screc is not None else None)
+        t = time.perf_counter()
+        for _ in range(20):
+            solver.solve(sx0[:1], srec[:1], screc[:1] if screc is not None else None)
+        ms_b1_host = (time.perf_counter() - t) / 20 * 1e3
+    return ms_b1, ms_b1_host, ms_b1_host_copy
+
+
+def dump_outputs(dirpath, rank, arrays, limit=64 * 10 ** 6):
+    """--dump-outputs DIR: what the last timed step returned to its caller, one DIR/<name>.npy per array (floating
+    arrays in their own precision, integer ones as float64; ranks above 0 write <name>.rank<r>.npy). Every array has
+    the batch as its first axis. Above `limit` bytes in all, the same seeded sample of batch rows is kept of every
+    array and the rows' indices are written as rows.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=v.dtype if v.dtype in (np.float32, np.float64) else np.float64)
+              for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_row = sum(v.nbytes // max(B, 1) for v in arrays.values()) + 8
+    if per_row * B > limit:
+        rows = np.sort(np.random.default_rng(SEED).choice(B, size=max(1, limit // per_row), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), v)
 
 
 def ocp_tick(gen, projected, T=60, warm=5):
@@ -517,6 +552,15 @@ def main():
                          "for --cadence-calls calls, each synchronised; the per-call latency distribution is added to "
                          "the line as 'cadence' (the clocks a 50 Hz loop runs at, not a saturated stream)")
     ap.add_argument("--cadence-calls", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the short-warm-up pass, the end-to-end "
+                         "(result gather) pass, the CPU baselines and the comparison with the fp64 CPU oracle; with "
+                         "--ocp the B = 1 latencies, the C++ mirror tick and the CPU oracle. Off: set up, warm up, "
+                         "time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (u, status, iters; --ocp: x, "
+                         "u, status, iters) as DIR/<name>.npy, at most 64 MB in all (a seeded sample of the batch rows "
+                         "above that); the inputs are the same from run to run with the same arguments")
     ap.add_argument("--allow-shared", action="store_true",
                     help="let ranks share a GPU (rehearsal on a one-GPU box); the line then says shared_gpu and n_gpus "
                          "counts distinct devices")
@@ -596,16 +640,18 @@ def main():
             e.solve_device(B, x0, xref, foot, contact, uo, None, so, io, sh)
 
     # value_short_warmup: the same timed loop right after 5 warm-up steps with no extension (the GPU near its idle
-    # clock), before the regular warm-up below; it separates clock warm-up from kernel gains in the headline
-    for i in range(5):
-        step(i)
-    H.hipDeviceSynchronize()
-    barrier()
-    t_s = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    H.hipDeviceSynchronize()
-    value_short = world * B * args.steps / max_over_ranks(time.perf_counter() - t_s)
+    # clock), before the regular warm-up below; it separates clock warm-up from kernel gains in the headline (--full)
+    value_short = None
+    if args.full:
+        for i in range(5):
+            step(i)
+        H.hipDeviceSynchronize()
+        barrier()
+        t_s = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        H.hipDeviceSynchronize()
+        value_short = world * B * args.steps / max_over_ranks(time.perf_counter() - t_s)
     for i in range(args.warmup):
         step(i)
     H.hipDeviceSynchronize()
@@ -659,6 +705,15 @@ def main():
     t1 = time.perf_counter()
     barrier()
     elapsed = max_over_ranks(t1 - t0)
+    if args.dump_outputs:  # the last timed step's outputs, before any later pass writes the buffers again
+        uo, so, io = outs[(args.steps - 1) % K]
+        if args.sqp_iters > 0:
+            dump = {"u": uo.host(), "status": so.host(), "qp_iters": sqp_qi.host(), "sqp_iters": sqp_si.host()}
+            if args.nlp:
+                dump["feet"] = feet_out.host()
+        else:
+            dump = {"u": uo.host(), "status": so.host(), "iters": io.host()}
+        dump_outputs(args.dump_outputs, rank, dump)
     if not timed_events:  # stage times from the same number of profiled steps right after the timed ones
         cm.lib().cmpc_profile_begin(eng.ctx, (args.steps + K - 1) // K)
         for i in range(args.steps):
@@ -678,7 +733,7 @@ def main():
                       "cmpc_gather_shard on the step's stream), inside the timed window",
               "bytes_per_step": world * B * row, "ms_per_step": None}
     value_e2e = None
-    if not args.no_e2e and args.sqp_iters <= 0:
+    if args.full and not args.no_e2e and args.sqp_iters <= 0:
         # ResultGather's constructor and the checks below reach every collective on every rank and raise on all ranks
         # together, so the collectives stay matched whatever fails
         try:
@@ -846,6 +901,7 @@ def main():
         "stages_ms": stages,
         "fused_n64": fused,
         "inflight": K,
+        "full": args.full,
         "graph": bool(args.graph),
         "path": {k: eng.get_path(getattr(cm, "PATH_" + k)) for k in ("FUSED64", "FUSED128", "DIRECT", "RICCATI", "IPM72")},
         "stage_events": args.stage_events,
@@ -867,7 +923,7 @@ def main():
         result["solver"]["mean_iters"] = float(iters[ok].mean()) if ok.any() else 0.0
         result["roofline"] = None
 
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.sqp_iters <= 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.sqp_iters <= 0:
         S = min(args.cpu_sample, B)
         share, share_why = cpu_share()
         threads = args.cpu_threads or share

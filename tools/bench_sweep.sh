@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out; mkdir -p $O
 cd $R
-run() { name=$1; shift; timeout -k 10 240 python bench.py --cpu-sample 0 "$@" > $O/sweep_$name.json 2> $O/sweep_$name.err || { echo "FAIL $name rc=$?"; tail -5 $O/sweep_$name.err; exit 1; }; echo "$name $(cat $O/sweep_$name.json)"; }
+run() { name=$1; shift; timeout -k 10 240 python bench.py --full --cpu-sample 0 "$@" > $O/sweep_$name.json 2> $O/sweep_$name.err || { echo "FAIL $name rc=$?"; tail -5 $O/sweep_$name.err; exit 1; }; echo "$name $(cat $O/sweep_$name.json)"; }
 run c2_trot_n10_f64
 run c3_trot_n20_f32 --horizon 20 --precision f32
 run c3_trot_n20_f64 --horizon 20

@@ -6,7 +6,7 @@ ROUNDS=${ROUNDS:-2}
 for r in $(seq 1 $ROUNDS); do
   for A in "$@"; do
     L=${A%%|*}; ARGS=${A#*|}
-    timeout -k 10 200 python bench.py --cpu-sample 0 $ARGS > $O/${L}_$r.json 2> $O/${L}_$r.err || { tail $O/${L}_$r.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --cpu-sample 0 $ARGS > $O/${L}_$r.json 2> $O/${L}_$r.err || { tail $O/${L}_$r.err; exit 1; }
     python3 -c "import json;d=json.load(open('$O/${L}_$r.json'));print('$L', $r, round(d['value']), round(d['value_end_to_end'] or 0), {k: round(v,4) for k,v in d['stages_ms'].items()})"
   done
 done

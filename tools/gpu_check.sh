@@ -7,7 +7,7 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout
 tail -3 $O/gpu_tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log; exit 1; }
 cat $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(round(d['value']),round(d['value_end_to_end'] or 0),d['gather'],d['stages_ms'],d['roofline']['frac'],d['cpu_baseline']['value'],d['build'])"
-timeout -k 10 300 python bench.py --gpus 2 --cpu-sample 0 > $O/bench2.json 2> $O/bench2.err || { tail $O/bench2.err; exit 1; }
+timeout -k 10 300 python bench.py --full --gpus 2 --cpu-sample 0 > $O/bench2.json 2> $O/bench2.err || { tail $O/bench2.err; exit 1; }
 python3 -c "import json;d=json.load(open('$O/bench2.json'));print(d['n_gpus'],round(d['value']),round(d['value_end_to_end'] or 0),d['gather'])"

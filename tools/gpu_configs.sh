@@ -3,7 +3,7 @@
 # mixed gait; config 4 share: B=32768) and the all-stance classes, then kernel stats of configs 3 and 5.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/cfg; mkdir -p $O; cd $R
 fatal() { case $1 in 124|134|137|139) echo "fatal exit $1 in $2"; exit 1;; esac; }
-run() { name=$1; shift; timeout -k 10 200 python bench.py --cpu-sample 0 "$@" > $O/$name.json 2> $O/$name.err; rc=$?; fatal $rc $name; [ $rc -ne 0 ] && { tail -3 $O/$name.err; exit 1; }
+run() { name=$1; shift; timeout -k 10 200 python bench.py --full --cpu-sample 0 "$@" > $O/$name.json 2> $O/$name.err; rc=$?; fatal $rc $name; [ $rc -ne 0 ] && { tail -3 $O/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/$name.json'));print('$name',round(d['value']),{k:round(v,4) for k,v in d['stages_ms'].items()},round(d['roofline']['frac'],4))"; }
 run c3 --horizon 20 --precision f32
 run c5 --gait 1

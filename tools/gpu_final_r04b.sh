@@ -8,9 +8,9 @@ fatal() { case $1 in 124|134|137|139) echo "fatal exit $1 in $2"; exit 1;; esac;
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1; rc=$?
 tail -3 $O/gpu_tests.log; fatal $rc tests
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; tail -1 $O/smoke.log; fatal $rc smoke
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?; echo bench_rc=$rc; fatal $rc bench
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?; echo bench_rc=$rc; fatal $rc bench
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(round(d['value']),d['stages_ms'],d['roofline']['frac'],d['cpu_baseline']['value'])"
-b() { local n=$1; shift; timeout -k 10 300 python -u bench.py "$@" > $O/$n.json 2> $O/$n.err; local rc=$?; fatal $rc $n
+b() { local n=$1; shift; timeout -k 10 300 python -u bench.py --full "$@" > $O/$n.json 2> $O/$n.err; local rc=$?; fatal $rc $n
       python3 -c "import json;d=json.loads(open('$O/$n.json').read().strip().split(chr(10))[-1]);print('$n',round(d['value']),d['unit'],round(d['ms_per_step'],4),d.get('stages_ms'),d.get('ms_per_solve_b1'),d['roofline']['frac'])" || tail -3 $O/$n.err; }
 b c3 --horizon 20 --precision f32 --steps 100 --warmup 20 --cpu-sample 0
 b c5 --gait 1 --steps 100 --warmup 20 --cpu-sample 0

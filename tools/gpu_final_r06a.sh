@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
 tail -3 $O/gpu_tests.log; fatal $rc tests
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; tail -1 $O/smoke.log; fatal $rc smoke
 fi
-b() { local n=$1; shift; timeout -k 10 300 python -u bench.py "$@" > $O/$n.json 2> $O/$n.err; local rc=$?; fatal $rc $n
+b() { local n=$1; shift; timeout -k 10 300 python -u bench.py --full "$@" > $O/$n.json 2> $O/$n.err; local rc=$?; fatal $rc $n
       python3 -c "import json;d=json.loads(open('$O/$n.json').read().strip().split(chr(10))[-1]);t=d.get('tick') or {};print('$n',round(d['value']),d['unit'],round(d['ms_per_step'],4),d['roofline']['traffic'] if d.get('roofline') else None,d['roofline']['frac'] if d.get('roofline') else None,t.get('tick_ms_median'),t.get('keep_cost_ms_median'))" || tail -3 $O/$n.err; }
 b bench --cadence 20
 b c3 --horizon 20 --precision f32 --steps 100 --warmup 20 --cpu-sample 0

@@ -9,7 +9,7 @@ tail -3 $O/gpu_tests.log; [ $rc -ne 0 ] && exit 1
 for r in 1 2; do
   for A in "nlp72|--sqp-iters 10 --nlp --steps 20 --warmup 5" "nlp128|--sqp-iters 10 --nlp --steps 20 --warmup 5 --path IPM72=0"; do
     L=${A%%|*}; BA=${A#*|}
-    timeout -k 10 200 python bench.py --cpu-sample 0 $BA > $O/${L}_$r.json 2> $O/${L}_$r.err || { tail -5 $O/${L}_$r.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --cpu-sample 0 $BA > $O/${L}_$r.json 2> $O/${L}_$r.err || { tail -5 $O/${L}_$r.err; exit 1; }
     python3 -c "import json;d=json.load(open('$O/${L}_$r.json'));print('$L',$r,round(d['value']),d['ms_per_step'])"
   done
   for W in "c5|--gait 1" "c2|"; do
