@@ -26,41 +26,16 @@
 // (rows 8 rho + 4w + a, rho = 0..15: 128 tile registers per lane, 2 waves per SIMD), a chunk's pivot rows in register
 // rows 0 and 1, the tile rotated by two register rows per chunk, and two pyramid rows per thread; half as many waves
 // meet at each pair barrier and each brings twice the bulk FMAs.
-#include <type_traits>
-
 #include "cmpc_device.hpp"
 #include "cmpc_kernels.hpp"
 #include "srbd_condense.hpp"
 #include "step_ratio.hpp"
 #include "wave_dpp.hpp"
+#include "ipm_common.hpp"
 
-// In-kernel s_memtime stamps (wave 0's view), diagnostic builds only (-DCMPC_IPM_STAMPS; lab/run_lab.sh): per-QP
-// cycles into IpmArgs::stamps[q][9]. Segments: 0 H + residuals, 1 Newton matrix, 2 elimination, 3 pivots/mask,
-// 4 solves, 5 predictor rest, 6 corrector rest, 7 update, 8 total.
-#ifdef CMPC_IPM_STAMPS
-#define X_STAMP_DECL                                               \
-  unsigned long long xs_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};       \
-  const unsigned long long xs_t0_ = ipm128x::memtime();            \
-  unsigned long long xs_prev_ = xs_t0_
-#define X_STAMP(k)                                       \
-  do {                                                   \
-    const unsigned long long t_ = ipm128x::memtime();    \
-    xs_acc_[k] += t_ - xs_prev_;                         \
-    xs_prev_ = t_;                                       \
-  } while (0)
-#define X_STAMP_STORE(ptr, q)                                                   \
-  do {                                                                          \
-    const unsigned long long t_ = ipm128x::memtime();                           \
-    if ((ptr) && threadIdx.x == 0) {                                            \
-      for (int k_ = 0; k_ < 8; ++k_) (ptr)[(size_t)(q) * 9 + k_] = xs_acc_[k_]; \
-      (ptr)[(size_t)(q) * 9 + 8] = t_ - xs_t0_;                                 \
-    }                                                                           \
-  } while (0)
-#else
-#define X_STAMP_DECL (void)0
-#define X_STAMP(k) (void)0
-#define X_STAMP_STORE(ptr, q) (void)0
-#endif
+// Phase stamps (-DCMPC_IPM_STAMPS, ipm_common.hpp: IPM_STAMP*; wave 0's view) into IpmArgs::stamps[q][9]. Segments:
+// 0 H + residuals, 1 Newton matrix, 2 elimination, 3 pivots/mask, 4 solves, 5 predictor rest, 6 corrector rest,
+// 7 update, 8 total.
 
 // fp32 elimination bulk on packed FMAs (row_update2); 0 selects the DPP-FMA form (lab A/B builds only)
 #ifndef CMPC_PK128
@@ -70,45 +45,6 @@
 namespace cmpc {
 namespace ipm128x {
 constexpr bool PACKED = CMPC_PK128 != 0;
-
-__device__ __forceinline__ unsigned long long memtime() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
-template <typename T>
-struct Lim;
-template <>
-struct Lim<double> {
-  static constexpr double pivot_min = 1e-200;
-  static constexpr double mu_min = 1e-300;
-};
-template <>
-struct Lim<float> {
-  static constexpr float pivot_min = 1e-30f;
-  static constexpr float mu_min = 1e-35f;
-};
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    sfor<B + 1, E>(f);
-  }
-}
-
-__device__ __forceinline__ double rcp_raw(double x) { return __builtin_amdgcn_rcp(x); }
-__device__ __forceinline__ float rcp_raw(float x) { return __builtin_amdgcn_rcpf(x); }
-template <typename T>
-__device__ __forceinline__ T pivot_inv(T p) {
-  T y = rcp_raw(p);
-  const T e = fma(-p, y, T(1));
-  y = fma(y, e, y);
-  return p > T(Lim<T>::pivot_min) ? y : T(0);
-}
 
 // k += row_newbcast<B0>(src) * m
 template <int B0, typename T>
@@ -136,18 +72,6 @@ __device__ __forceinline__ void dfma_self(T& k, T m) {  // the DPP source itself
   else
     asm volatile("v_fmac_f32_dpp %0, %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(k) : "v"(m), "n"(B0));
 }
-
-__device__ __forceinline__ int olane() {
-  int l = (int)threadIdx.x & 63;
-  asm volatile("" : "+v"(l));
-  return l;
-}
-__device__ __forceinline__ int owave() {
-  int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  asm volatile("" : "+s"(w));
-  return w;
-}
-__device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }
 
 // Partial-sum and pivot-row strides, padded so that every LDS access below is bank-conflict free under the MI355X
 // banking rules (MI355X_MICROARCH.md §LDS: ds_write_b32 / ds_read_b32 in 32-lane groups on (a/4) mod 32,
@@ -210,6 +134,7 @@ struct Shared128<T, true> {
 // tid + NT s (s < PR = 256 / NT).
 template <typename T, int MINB, bool FUSED, int NW = 4>
 __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const CondenseArgs<T>* C, const int q) {
+  using namespace ipm;
   using namespace ipm128x;
   static_assert(NW == 4 || NW == 2, "four or two waves per QP");
   static_assert(!FUSED || NW == 4, "the fused condensing runs on four waves");
@@ -234,7 +159,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     n = a.nvar[q];
   }
   if (n <= 64 || n > NP) return;  // served by another size class
-  X_STAMP_DECL;
+  IPM_STAMP_DECL(8);
   const int ld = a.ld;
   const int nt = n / 3;
   const int m = 5 * nt;
@@ -317,7 +242,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
   // FULL = all 8 chunks (H u), else the lower registers c <= (RG rho) / 16 (forward solve). Input chunk values in xc.
   auto row_partials = [&](const T (&xc)[8], auto full_) {
     constexpr bool full = decltype(full_)::value;
-    const int ol = olane(), w = owave();
+    const int ol = olane_mw(), w = owave();
     const int a = ol >> 4, b = ol & 15;
     const int base = b * SR + 4 * w + a;  // row i = RG rho + 4w + a
     sfor<0, NR>([&](auto r_) {
@@ -345,7 +270,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     if (isv) L.v[tid] = y * invd_i;
     __syncthreads();
     {
-      const int ol = olane();
+      const int ol = olane_mw();
       const int b = ol & 15;
       T tc[8];
 #pragma unroll
@@ -357,7 +282,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     if (isv) L.z[(tid % RG) * ZS + tid / RG] = z;
     __syncthreads();
     {
-      const int ol = olane(), w = owave();
+      const int ol = olane_mw(), w = owave();
       const int a = ol >> 4, b = ol & 15;
       T zr[NR];
 #pragma unroll
@@ -398,9 +323,9 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     __syncthreads();
     const T ctw = CT_var();
     T y = var ? -rg_i - ctw : T(0);
-    X_STAMP(5);
+    IPM_STAMP(5);
     solve(y);
-    X_STAMP(4);
+    IPM_STAMP(4);
     du_i = y;
     if (isv) L.v[tid] = du_i;
     __syncthreads();
@@ -440,19 +365,13 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       T v = fmax(fmax(L.p_res[k][lane0], L.p_res[k][lane0 + 64]), fmax(L.p_res[k][lane0 + 128], L.p_res[k][lane0 + 192]));
       r[k] = wave_max_dpp(v);
     }
-    if (lane0 == 0) {
-      sr[5] = (double)L.mu_st;
-      sr[6] = (double)r[0];
-      sr[7] = 0.0;
-      sr[8] = (double)r[1];
-      sr[9] = (double)r[2];
-    }
+    if (lane0 == 0) stat_residuals(sr, L.mu_st, r[0], r[1], r[2]);
   };
   for (it = 0;; ++it) {
     progress_prio(it);  // cmpc_device.hpp (lab, n = 120 fp64: 3.94 -> 3.91 ms)
     // ---- H: NK loads per lane, 4 rows x 16 consecutive columns per instruction
     {
-      const int ol = olane(), w = owave();
+      const int ol = olane_mw(), w = owave();
       const T* hp = Hq + (size_t)(4 * w + (ol >> 4)) * NP + (ol & 15);
 #pragma unroll
       for (int rho = 0; rho < NR; ++rho)
@@ -466,7 +385,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
 #pragma unroll
     for (int s = 0; s < PR; ++s) cu[s] = C_row(s);
     {
-      const int ol = olane();
+      const int ol = olane_mw();
       const int b = ol & 15;
       T uc[8];
 #pragma unroll
@@ -506,26 +425,13 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     ms = block_sum(ms);
     const T mu = m > 0 ? ms / T(2 * m) : T(0);
     const bool st_on = a.stats && it < a.stats_cap;  // statistics row of this iteration (cmpc_enable_stats)
-    auto st_row = [&]() { return a.stats + ((size_t)q * a.stats_cap + it) * CMPC_STAT_COLS; };
+    auto st_row = [&]() { return stat_row(a, q, it); };
     if (st_on && tid == 0) L.mu_st = mu;  // the row's residual part is written at the end of the iteration / the exit
-    // non-finite residual anywhere -> NAN_SOL; stopping rule as a block vote (max <= tol iff all <= tol)
-    if (__syncthreads_or(!(isfinite(rs) && fin_r))) {
-      status = CMPC_NAN_SOL;
-      break;
-    }
-    if (__syncthreads_and(rs <= T(S.tol_stat) && ok_r)) {
-      status = CMPC_SUCCESS;
-      break;
-    }
-    if (it >= S.iter_max) {
-      status = CMPC_MAX_ITER;
-      break;
-    }
-    if (m > 0 && !(mu > T(Lim<T>::mu_min))) {
-      status = CMPC_MIN_STEP;
-      break;
-    }
-    X_STAMP(0);
+    // stopping rule (ipm_common.hpp: IPM_BREAK_IF_STOPPED) as block votes (max <= tol iff all <= tol)
+    IPM_BREAK_IF_STOPPED(status, __syncthreads_or(!(isfinite(rs) && fin_r)),
+                         __syncthreads_and(rs <= T(S.tol_stat) && ok_r), it, S.iter_max,
+                         m > 0 && !(mu > T(Lim<T>::mu_min)));
+    IPM_STAMP(0);
 
     // ---- Newton matrix K = H + C' diag(lam_l/t_l + lam_u/t_u) C + reg I: thread j < 128 writes the 3x3 block
     //      column of variable j (rows t3 .. t3 + 2 of its triple), the tile adds it where entry (i, j) falls there
@@ -557,7 +463,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     }
     __syncthreads();
     {
-      const int ol = olane(), w = owave();
+      const int ol = olane_mw(), w = owave();
       const int a = ol >> 4, b = ol & 15;
       // entry (i, j) = (RG rho + 4w + a, 16c + b) is in j's triple iff 0 <= i - 3 (j / 3) <= 2: only registers
       // c = clo .. chi can hold such entries
@@ -576,7 +482,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
         });
       });
     }
-    X_STAMP(1);
+    IPM_STAMP(1);
     // park the per-thread iterate in LDS across the elimination (its registers hold the pivot pairs instead)
 #pragma unroll
     for (int s = 0; s < PR; ++s) {
@@ -601,7 +507,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     // own FMA), its pivot from uniform LDS reads (d_q = K[q][q] + K[q][p] (-K[p][q] / d_p)): bit-identical to one
     // pivot at a time.
     T mp[8], mq[8];
-    // lane coordinates are re-read (olane(): one opaque VALU op) at every use in the elimination: held across it, the
+    // lane coordinates are re-read (olane_mw(): one opaque VALU op) at every use in the elimination: held across it, the
     // compiler spilled lb0 to scratch and reloaded it once per pivot pair (k_solve128<float>)
     // the pair's pivots and their reciprocals: scalar chain, started as soon as the pair's scalars are read so
     // that its latency (two reciprocals in sequence) runs under the bulk FMAs of the previous pair
@@ -617,7 +523,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     // multipliers of the pair from the two broadcast rows
     auto pair_vec = [&](const T (&xp)[8], const T (&xq)[8], T kqp, T invp, T invq, auto tp_) {
       constexpr int tp = decltype(tp_)::value, tq = tp + 1;
-      const int lbp = olane() & 15;
+      const int lbp = olane_mw() & 15;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const T mv = -(xp[c] * invp);
@@ -673,7 +579,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       dfma_self<tq, T>(K[rho * 8], mq[0]);
     };
     auto read_pair = [&](int buf, T (&xp)[8], T (&xq)[8], T& dp, T& kqp, T& kpq, T& kqq, int tp) {
-      const int lb = olane() & 15;
+      const int lb = olane_mw() & 15;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         xp[c] = L.rowbuf[buf][0][16 * c + lb];
@@ -687,7 +593,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     for (int c0 = 0; c0 < 8; ++c0) {
       if (c0 < nch) {
         // rows 16 c0, 16 c0 + 1 = wave 0, rows a = 0, 1 of register row 0: final (every earlier pivot applied)
-        const int ol0 = olane();
+        const int ol0 = olane_mw();
         if (wave0 == 0 && (ol0 >> 4) < 2) {
 #pragma unroll
           for (int c = 0; c < 8; ++c) L.rowbuf[0][ol0 >> 4][16 * c + (ol0 & 15)] = K[c];
@@ -710,11 +616,11 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
             // the chunk's rows below the pair: the next pair's owner first, then its two rows to LDS
             if (wv == w2) {
               if constexpr (a2 == 2) {
-                if ((olane() >> 4) >= 2) row_update2(std::integral_constant<int, r2>{}, std::integral_constant<int, tp>{});
+                if ((olane_mw() >> 4) >= 2) row_update2(std::integral_constant<int, r2>{}, std::integral_constant<int, tp>{});
               } else {
                 row_update2(std::integral_constant<int, r2>{}, std::integral_constant<int, tp>{});
               }
-              const int olw = olane();
+              const int olw = olane_mw();
               if ((olw >> 4) == a2 || (olw >> 4) == a2 + 1) {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) L.rowbuf[nb][(olw >> 4) - a2][16 * c + (olw & 15)] = K[r2 * 8 + c];
@@ -732,13 +638,13 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
           T xp[8], xq[8], dp = T(0), kqp = T(0), kpq = T(0), kqq = T(0), invp = T(0), invq = T(0);
           if constexpr (b < 7) {
 #ifdef X_BARRIER_STAMP  // diagnostic: time waiting at the pair barrier (segment 3)
-            X_STAMP(2);
+            IPM_STAMP(2);
             __syncthreads();
-            X_STAMP(3);
+            IPM_STAMP(3);
 #else
             __syncthreads();
 #endif
-            const int lbx = olane() & 15;
+            const int lbx = olane_mw() & 15;
 #pragma unroll
             for (int c = 0; c < 8; ++c) xp[c] = L.rowbuf[nb][0][16 * c + lbx];
             dp = L.rowbuf[nb][0][tp + 2];
@@ -753,7 +659,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
             if (rho <= NR - 1 - CR * c0 && 16 * c0 + RG * rho < n) row_update2(r_, std::integral_constant<int, tp>{});
           });
           if constexpr (b < 7) {
-            const int lby = olane() & 15;
+            const int lby = olane_mw() & 15;
 #pragma unroll
             for (int c = 0; c < 8; ++c) xq[c] = L.rowbuf[nb][1][16 * c + lby];
             pair_vec(xp, xq, kqp, invp, invq, std::integral_constant<int, tp + 2>{});
@@ -770,7 +676,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
 #pragma unroll
         for (int c = 0; c < 8; ++c) K[r * 8 + c] = K0[((r + CR) % NR) * 8 + ((c + 1) & 7)];
     }
-    X_STAMP(2);
+    IPM_STAMP(2);
 #pragma unroll
     for (int s = 0; s < PR; ++s) {
       const int j = rowj(s);
@@ -804,7 +710,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       });
     }
 
-    X_STAMP(3);
+    IPM_STAMP(3);
     // ---- predictor (affine scaling direction)
 #pragma unroll
     for (int s = 0; s < PR; ++s) {
@@ -821,14 +727,8 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
                              (tu[s] + alpha * dtu[s]) * (lu[s] + alpha * dlu[s])
                        : T(0);
       maff = block_sum(maff) / T(2 * m);
-      const T ratio = maff / mu;
-      const T sigma = ratio * ratio * ratio;
-      if (st_on && tid == 0) {
-        double* sr = st_row();
-        sr[0] = (double)alpha;
-        sr[1] = (double)maff;
-        sr[2] = (double)sigma;
-      }
+      const T sigma = centering(maff, mu);
+      if (st_on && tid == 0) stat_predictor(st_row(), alpha, maff, sigma);
       // ---- corrector: rm = t.lam + dt_aff.dlam_aff - sigma mu
 #pragma unroll
       for (int s = 0; s < PR; ++s) {
@@ -838,12 +738,12 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       direction();
       alpha = fmin(T(1), T(TAU) * max_step());
     }
-    X_STAMP(6);
+    IPM_STAMP(6);
     if (st_on && tid == 0) {
       double* sr = st_row();
       if (m == 0) sr[0] = sr[1] = sr[2] = __builtin_nan("");
-      sr[3] = sr[4] = (double)alpha;
-    }  // one step length for primal and dual
+      stat_step(sr, alpha);
+    }
     if (alpha < T(S.alpha_min)) {
       status = CMPC_MIN_STEP;
       break;
@@ -857,7 +757,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       lu[s] = fma(alpha, dlu[s], lu[s]);
     }
     if (st_on && wave0 == 0) stats_res(st_row());  // this iteration's residuals, still in L.p_res
-    X_STAMP(7);
+    IPM_STAMP(7);
   }
 
   const bool fin = !var || isfinite(u_i);
@@ -874,7 +774,7 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
   if (a.stats && it < a.stats_cap) {  // the stopping iteration's row: residuals and mu, no step
     __syncthreads();
     if (wave0 == 0) {
-      double* sr = a.stats + ((size_t)q * a.stats_cap + it) * CMPC_STAT_COLS;
+      double* sr = stat_row(a, q, it);
       if (lane0 < 5) sr[lane0] = __builtin_nan("");
       stats_res(sr);
     }
@@ -897,6 +797,8 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
     __syncthreads();
     if (tid == 0) {
       auto mx = [](T x, T y) { return fmax(x, y); };
+      // the row of ipm::res_store, inline: each maximum is read from LDS and stored in turn (as arguments of the
+      // shared function the three reductions run before the first store, which changed this kernel's code object)
       double* o = a.res + (size_t)q * 4;
       o[0] = (double)red4(mx, 0);
       o[1] = 0.0;
@@ -904,17 +806,13 @@ __device__ __forceinline__ void ipm128x_body(const IpmArgs<T>& a, const Condense
       o[3] = (double)red4(mx, 2);
     }
   }
-  X_STAMP_STORE(a.stamps, q);
+  IPM_STAMP_STORE(a.stamps, q, 8, 9);
 }
 
 template <typename T, int MINB, int NW = 4>  // MINB workgroups per CU: 2 (fp64, 2 waves per SIMD), 4 (fp32)
 __global__ __launch_bounds__(64 * NW, MINB) void k_ipm128x(IpmArgs<T> a) {
-  int q = blockIdx.x;
-  if (a.qlist[1]) {  // compacted class list: real QPs first, the surplus workgroups exit
-    if (q >= a.qcount[1]) return;
-    q = a.qlist[1][q];
-    if ((unsigned)q >= gridDim.x) return;  // grid = batch: a corrupt list entry cannot address past it
-  }
+  int q;
+  if (!ipm::class_qp(a, 1, q)) return;
   ipm128x_body<T, MINB, false, NW>(a, nullptr, q);
 }
 
@@ -922,6 +820,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_ipm128x(IpmArgs<T> a) {
 // k_class_lists built from k_solve64's nvar hints.
 template <typename T, int MINB>
 __global__ __launch_bounds__(256, MINB) void k_solve128(IpmArgs<T> a, CondenseArgs<T> c) {
+  // as ipm::class_qp(a, 1, q), but the class list always exists here (no identity mapping): no null test
   int q = blockIdx.x;
   if (q >= a.qcount[1]) return;
   q = a.qlist[1][q];

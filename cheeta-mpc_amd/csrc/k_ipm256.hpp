@@ -23,12 +23,11 @@
 //     per-wave partial vectors summed in a fixed order, so results are run-to-run deterministic (no atomics);
 //   * one thread per variable (tid < 256) and per pyramid row (tid < 5 n/3 <= 425): the constraint state stays in
 //     registers; block reductions are DPP wave reductions + 8 partials through LDS.
-#include <type_traits>
-
 #include "cmpc_device.hpp"
 #include "cmpc_kernels.hpp"
 #include "step_ratio.hpp"
 #include "wave_dpp.hpp"
+#include "ipm_common.hpp"
 
 namespace cmpc {
 namespace ipm256 {
@@ -46,8 +45,6 @@ struct Mf<double> {
   }
   // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
   static __device__ __forceinline__ int row(int lane, int k) { return (lane >> 4) + 4 * k; }
-  static constexpr double pivot_min = 1e-200;
-  static constexpr double mu_min = 1e-300;
 };
 template <>
 struct Mf<float> {
@@ -57,33 +54,14 @@ struct Mf<float> {
   }
   // C/D layout of v_mfma_f32_16x16x4_f32: col = lane & 15, row = 4 * (lane >> 4) + reg
   static __device__ __forceinline__ int row(int lane, int k) { return 4 * (lane >> 4) + k; }
-  static constexpr float pivot_min = 1e-30f;
-  static constexpr float mu_min = 1e-35f;
 };
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
-
-// Lane / wave ids the compiler cannot hoist: every phase re-derives its lane offsets and slot coordinates from these,
-// instead of keeping ~17 x 4 tile addresses live in VGPRs (and the slot coordinates in SGPRs) across the iteration.
-__device__ __forceinline__ int opaque_lane() {
-  int l = (int)threadIdx.x & 63;
-  asm volatile("" : "+v"(l));
-  return l;
-}
-__device__ __forceinline__ int opaque_wave() {
-  int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  asm volatile("" : "+s"(w));
-  return w;
-}
+// Lane / wave ids the compiler cannot hoist (ipm::olane_mw, ipm::owave): every phase re-derives its lane offsets and
+// slot coordinates from these, instead of keeping ~17 x 4 tile addresses live in VGPRs (and the slot coordinates in
+// SGPRs) across the iteration.
 #define IPM256_LOCAL_IDS                       \
-  const int lane = ipm256::opaque_lane();      \
-  const int wave = ipm256::opaque_wave();      \
+  const int lane = ipm::olane_mw();            \
+  const int wave = ipm::owave();               \
   const int c16 = lane & 15, g4 = lane >> 4;   \
   (void)c16;                                   \
   (void)g4
@@ -94,13 +72,6 @@ __device__ __forceinline__ int owner(int I) { return I < NT / 2 ? I : NT - 1 - I
 template <int NT>
 __device__ __forceinline__ int slot_I(int w, int s) { return s <= w ? w : NT - 1 - w; }
 __device__ __forceinline__ int slot_J(int w, int s) { return s <= w ? s : s - w - 1; }
-
-// one wave's LDS is in order; this orders the compiler and drains LDS before cross-lane reuse
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // sum inside each 16-lane row (every lane of the row gets it)
 template <typename T>
@@ -144,6 +115,7 @@ struct Lds {
 
 template <typename T, int NT>
 __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 waves per SIMD
+  using namespace ipm;
   using namespace ipm256;
   using MF = Mf<T>;
   using acc_t = typename MF::acc_t;
@@ -153,12 +125,8 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
   constexpr int SL = NT + 1;       // tiles (slots) per wave
   static_assert(5 * (NP / 3) <= NTHR, "one thread per pyramid row");
 
-  int q = blockIdx.x;
-  if (a.qlist[2]) {  // compacted class list: real QPs first, the surplus workgroups exit
-    if (q >= a.qcount[2]) return;
-    q = a.qlist[2][q];
-    if ((unsigned)q >= gridDim.x) return;  // grid = batch: a corrupt list entry cannot address past it
-  }
+  int q;
+  if (!class_qp(a, 2, q)) return;
   if (a.status[q] != CMPC_SUCCESS) return;  // invalid contact table / too large: status already set
   const int n = a.nvar[q];
   if (n <= NP / 2 || n > NP) return;        // served by another size class
@@ -278,7 +246,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
         }
       }
       __syncthreads();
-      static_for<0, SL>([&](auto s_) {
+      sfor<0, SL>([&](auto s_) {
         constexpr int s = decltype(s_)::value;
         const int I = slot_I<NT>(wave, s), Jt = slot_J(wave, s);
         if (Jt == J && I > J) {
@@ -308,7 +276,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
           L.vec[16 * I + lane] = xc;
         }
         wave_sync();
-        static_for<0, SL>([&](auto s_) {
+        sfor<0, SL>([&](auto s_) {
           constexpr int s = decltype(s_)::value;
           const int It = slot_I<NT>(wave, s), J = slot_J(wave, s);
           if (It == I && J < I) {
@@ -360,7 +328,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
     // ---- load H tiles (16 consecutive columns per row group: 128-B segments)
     {
     IPM256_LOCAL_IDS;
-    static_for<0, SL>([&](auto s_) {
+    sfor<0, SL>([&](auto s_) {
       constexpr int s = decltype(s_)::value;
       const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
       const T* hp = Hq + (size_t)(16 * I) * NP + 16 * J + c16;
@@ -378,7 +346,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
     {
       IPM256_LOCAL_IDS;
       T pa0[4] = {T(0), T(0), T(0), T(0)}, pa1[4] = {T(0), T(0), T(0), T(0)};
-      static_for<0, SL>([&](auto s_) {
+      sfor<0, SL>([&](auto s_) {
         constexpr int s = decltype(s_)::value;
         const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
         const T uc = L.vec[16 * J + c16];
@@ -432,41 +400,17 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
       rs = fabs(rg_i);
     }
     block_reduce(rs, ri, rc, ms);
-    if (a.res && tid == 0) {  // block maxima of this iteration's residuals (the last write is the final one)
-      double* o = a.res + (size_t)q * 4;
-      o[0] = (double)rs;
-      o[1] = 0.0;
-      o[2] = (double)ri;
-      o[3] = (double)rc;
-    }
+    // block maxima of this iteration's residuals (the last write is the final one)
+    if (a.res && tid == 0) res_store(a.res, q, rs, ri, rc);
     const T mu = m > 0 ? ms / T(2 * m) : T(0);
     const bool st_on = a.stats && it < a.stats_cap;  // statistics row of this iteration (cmpc_enable_stats)
-    auto st_row = [&]() { return a.stats + ((size_t)q * a.stats_cap + it) * CMPC_STAT_COLS; };
-    if (st_on && tid == 0) {  // statistics row: residuals (block maxima) and mu now, the step below
-      double* sr = st_row();
-      for (int k = 0; k < 5; ++k) sr[k] = __builtin_nan("");
-      sr[5] = (double)mu;
-      sr[6] = (double)rs;
-      sr[7] = 0.0;
-      sr[8] = (double)ri;
-      sr[9] = (double)rc;
-    }
-    if (!(isfinite(rs) && isfinite(ri) && isfinite(rc))) {
-      status = CMPC_NAN_SOL;
-      break;
-    }
-    if (rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp)) {
-      status = CMPC_SUCCESS;
-      break;
-    }
-    if (it >= S.iter_max) {
-      status = CMPC_MAX_ITER;
-      break;
-    }
-    if (m > 0 && !(mu > T(MF::mu_min))) {
-      status = CMPC_MIN_STEP;
-      break;
-    }
+    auto st_row = [&]() { return stat_row(a, q, it); };
+    // statistics row: residuals (block maxima) and mu now, the step below
+    if (st_on && tid == 0) stat_open(st_row(), mu, rs, ri, rc);
+    // stopping rule (ipm_common.hpp: IPM_BREAK_IF_STOPPED) on the block maxima every thread holds
+    IPM_BREAK_IF_STOPPED(status, !(isfinite(rs) && isfinite(ri) && isfinite(rc)),
+                         rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp), it, S.iter_max,
+                         m > 0 && !(mu > T(Lim<T>::mu_min)));
 
     // ---- Newton matrix K = H + C' diag(lam_l/t_l + lam_u/t_u) C + reg I (3x3 blocks on the triple diagonal)
     itl = con ? T(1) / tl : T(0);
@@ -476,7 +420,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
     __syncthreads();
     {
     IPM256_LOCAL_IDS;
-    static_for<0, SL>([&](auto s_) {
+    sfor<0, SL>([&](auto s_) {
       constexpr int s = decltype(s_)::value;
       const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
       if (I - J <= 1) {
@@ -511,11 +455,11 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
         // diagonal tile (selected out of its slot once, so the factorisation code exists once); column s
         // broadcast through LDS
         acc_t D = K[0];
-        static_for<1, SL>([&](auto s_) {
+        sfor<1, SL>([&](auto s_) {
           constexpr int s = decltype(s_)::value;
           if (slot_I<NT>(wave, s) == p && slot_J(wave, s) == p) D = K[s];
         });
-        static_for<0, 16>([&](auto c_) {
+        sfor<0, 16>([&](auto c_) {
           constexpr int sc = decltype(c_)::value;
           if (c16 == sc) {
 #pragma unroll
@@ -524,8 +468,8 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
           wave_sync();
           const T d = L.col[sc];
           // BLASFEO-style guard as k_ipm_reg / oracle_qp_ipm: a lost pivot drops its direction; NaN recorded
-          const T il0 = rsqrt_acc(fmax(d, T(MF::pivot_min)));
-          const T il = d > T(MF::pivot_min) ? il0 : T(0);
+          const T il0 = rsqrt_acc(fmax(d, T(Lim<T>::pivot_min)));
+          const T il = d > T(Lim<T>::pivot_min) ? il0 : T(0);
           if (lane == 0) {
             L.il[sc] = il;
             if (d != d) L.nanflag = 1;
@@ -545,10 +489,10 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
         wave_sync();
         if (lane < 16) {
           T X[16];
-          static_for<0, 16>([&](auto r_) {
+          sfor<0, 16>([&](auto r_) {
             constexpr int r = decltype(r_)::value;
             T v = r == lane ? T(1) : T(0);
-            static_for<0, r>([&](auto k_) {
+            sfor<0, r>([&](auto k_) {
               constexpr int kk = decltype(k_)::value;
               v = fma(-L.dg[r * PS + kk], X[kk], v);
             });
@@ -559,7 +503,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
         }
       }
       // raw panel tiles A_ip (i > p) -> LDS
-      static_for<0, SL>([&](auto s_) {
+      sfor<0, SL>([&](auto s_) {
         constexpr int s = decltype(s_)::value;
         const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
         if (J == p && I > p) {
@@ -571,7 +515,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
       {
       IPM256_LOCAL_IDS;
       // L_ip = A_ip L_pp^-T on the matrix cores (A in the operand layout from LDS, B[k][j] = Linv[j][k])
-      static_for<0, SL>([&](auto s_) {
+      sfor<0, SL>([&](auto s_) {
         constexpr int s = decltype(s_)::value;
         const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
         if (J == p && I > p) {
@@ -591,7 +535,7 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
       {
       IPM256_LOCAL_IDS;
       // trailing update A_ij -= L_ip L_jp' (i >= j > p)
-      static_for<0, SL>([&](auto s_) {
+      sfor<0, SL>([&](auto s_) {
         constexpr int s = decltype(s_)::value;
         const int I = slot_I<NT>(wave, s), J = slot_J(wave, s);
         if (J > p) {
@@ -620,24 +564,15 @@ __global__ __launch_bounds__(32 * NT, 2) void k_ipm_tiled(IpmArgs<T> a) {  // 2 
     if (m > 0) {
       T maff = con ? (tl + alpha * dtl) * (ll + alpha * dll) + (tu + alpha * dtu) * (lu + alpha * dlu) : T(0);
       maff = block_sum(maff) / T(2 * m);
-      const T ratio = maff / mu;
-      const T sigma = ratio * ratio * ratio;
-      if (st_on && tid == 0) {
-        double* sr = st_row();
-        sr[0] = (double)alpha;
-        sr[1] = (double)maff;
-        sr[2] = (double)sigma;
-      }
+      const T sigma = centering(maff, mu);
+      if (st_on && tid == 0) stat_predictor(st_row(), alpha, maff, sigma);
       // ---- corrector: rm = t.lam + dt_aff.dlam_aff - sigma mu
       rml = con ? tl * ll + dtl * dll - sigma * mu : T(0);
       rmu = con ? tu * lu + dtu * dlu - sigma * mu : T(0);
       direction();
       alpha = fmin(T(1), T(TAU) * max_step());
     }
-    if (st_on && tid == 0) {
-      double* sr = st_row();
-      sr[3] = sr[4] = (double)alpha;
-    }  // one step length for primal and dual
+    if (st_on && tid == 0) stat_step(st_row(), alpha);
     if (alpha < T(S.alpha_min)) {
       status = CMPC_MIN_STEP;
       break;

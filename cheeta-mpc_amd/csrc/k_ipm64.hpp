@@ -31,44 +31,23 @@
 //     row loads per iteration;
 //   * lane-derived addresses come from an opaque lane id re-read every iteration (olane) so they are not hoisted
 //     out of the loop as ~100 live VGPRs; lane masks use the plain id and are hoisted into SGPR pairs.
-#include <type_traits>
-
 #include "cmpc_device.hpp"
 #include "cmpc_kernels.hpp"
 #include "condense64.hpp"
 #include "step_ratio.hpp"
 #include "dpp_rows.hpp"
 #include "wave_dpp.hpp"
+#include "ipm_common.hpp"
 
-// In-kernel s_memtime stamps, diagnostic builds only (-DCMPC_IPM_STAMPS; lab/run_lab.sh): per-QP cycles of each
-// phase into IpmArgs::stamps[q][9]. Segments: 0 H + residuals, 1 Newton matrix, 2 LDL', 3 lower-part mask, 4 solves,
-// 5 predictor rest, 6 corrector rest, 7 update, 8 total.
-#ifdef CMPC_IPM_STAMPS
-#define IPM_STAMP_DECL                                                    \
-  unsigned long long st_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};              \
-  const unsigned long long st_t0_ = ipm64::memtime();                   \
-  unsigned long long st_prev_ = st_t0_
-#define IPM_STAMP(k)                                      \
-  do {                                                    \
-    const unsigned long long t_ = ipm64::memtime();       \
-    st_acc_[k] += t_ - st_prev_;                          \
-    st_prev_ = t_;                                        \
-  } while (0)
-#define IPM_STAMP_STORE(ptr, q)                                                   \
-  do {                                                                            \
-    const unsigned long long t_ = ipm64::memtime();                               \
-    if ((ptr) && threadIdx.x == 0) {                                              \
-      for (int k_ = 0; k_ < 8; ++k_) (ptr)[(size_t)(q) * 9 + k_] = st_acc_[k_];   \
-      (ptr)[(size_t)(q) * 9 + 8] = t_ - st_t0_;                                   \
-    }                                                                             \
-  } while (0)
-#elif defined(CMPC_IPM_TIMELINE)
-// diagnostic: per-QP wave start / end on the 100-MHz real-time counter and the hardware slot (HW_ID, XCC_ID)
-#define IPM_STAMP_DECL                                                                      \
+// Phase stamps (-DCMPC_IPM_STAMPS, ipm_common.hpp: IPM_STAMP*) into IpmArgs::stamps[q][9]. Segments: 0 H + residuals,
+// 1 Newton matrix, 2 LDL', 3 lower-part mask, 4 solves, 5 predictor rest, 6 corrector rest, 7 update, 8 total.
+// Local to this kernel (-DCMPC_IPM_TIMELINE without the stamps; lab/timeline.py): per-QP wave start / end on the
+// 100-MHz real-time counter and the hardware slot (HW_ID, XCC_ID) in the same buffer.
+#if defined(CMPC_IPM_TIMELINE) && !defined(CMPC_IPM_STAMPS)
+#define IPM64_TIMELINE_DECL                                                                 \
   unsigned long long tl_t0_;                                                                \
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tl_t0_)::"memory")
-#define IPM_STAMP(k) (void)0
-#define IPM_STAMP_STORE(ptr, q)                                                             \
+#define IPM64_TIMELINE_STORE(ptr, q)                                                        \
   do {                                                                                      \
     unsigned long long t_;                                                                  \
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
@@ -83,71 +62,13 @@
     }                                                                                       \
   } while (0)
 #else
-#define IPM_STAMP_DECL (void)0
-#define IPM_STAMP(k) (void)0
-#define IPM_STAMP_STORE(ptr, q) (void)0
+#define IPM64_TIMELINE_DECL (void)0
+#define IPM64_TIMELINE_STORE(ptr, q) (void)0
 #endif
 
 namespace cmpc {
 
 namespace ipm64 {
-
-__device__ __forceinline__ unsigned long long memtime() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
-template <typename T>
-struct Lim;
-template <>
-struct Lim<double> {
-  static constexpr double pivot_min = 1e-200;  // BLASFEO-style guard: smaller pivots drop their direction
-  static constexpr double mu_min = 1e-300;     // mu underflow -> MIN_STEP instead of 0/0
-};
-template <>
-struct Lim<float> {
-  static constexpr float pivot_min = 1e-30f;
-  static constexpr float mu_min = 1e-35f;
-};
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    sfor<B + 1, E>(f);
-  }
-}
-template <int B, int E, typename F>
-__device__ __forceinline__ void sfor_down(F&& f) {  // E-1 down to B
-  if constexpr (B < E) {
-    f(std::integral_constant<int, E - 1>{});
-    sfor_down<B, E - 1>(f);
-  }
-}
-// Compiler-only ordering of LDS accesses: one wave's DS instructions execute in order, so a read issued after a
-// write (or a write after a read) in program order sees the right data without s_waitcnt.
-__device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }
-__device__ __forceinline__ int olane() {
-  int l = (int)threadIdx.x;
-  asm volatile("" : "+v"(l));
-  return l;
-}
-__device__ __forceinline__ bool uflag(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
-__device__ __forceinline__ double rcp_raw(double x) { return __builtin_amdgcn_rcp(x); }
-__device__ __forceinline__ float rcp_raw(float x) { return __builtin_amdgcn_rcpf(x); }
-// reciprocal of a pivot: hardware estimate + one Newton step, 0 for pivots at or below the guard (and NaN)
-template <typename T>
-__device__ __forceinline__ T pivot_inv(T p) {
-  T y = rcp_raw(p);
-  const T e = fma(-p, y, T(1));
-  y = fma(y, e, y);
-  return p > T(Lim<T>::pivot_min) ? y : T(0);
-}
-
 
 // Strides of the partial-sum buffers, chosen so that every access is bank-conflict free under the MI355X rules
 // (MI355X_MICROARCH.md §LDS; a ds_write_b64 covers 16 lanes of one row a = lane / 16, a ds_read_b64 32 lanes):
@@ -195,8 +116,10 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
   // ds_write2 / ds_read2 pairing is lost: +640 instructions, +3 % time)
   __shared__ IpmShared<T, (MODE > 0)> SH;
   constexpr bool FUSED = MODE > 0;
+  using namespace ipm;
   using namespace ipm64;
-  IPM_STAMP_DECL;
+  IPM_STAMP_DECL(8);
+  IPM64_TIMELINE_DECL;
   Lds<T>& L = SH.ipm;
   T K[64];
   T g_v, mu_v;
@@ -208,7 +131,7 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
       if (n < 0) {  // invalid contact table (status written) or a bigger class (nvar hint written)
         if (n == -2 && A.out_u)  // the rejected QP's result: zeros, INVALID_CONTACT, no iterations
           scatter_result<T>(A, q, 0, T(0), CMPC_INVALID_CONTACT, 0, SH.ipm.scr, olane(), 64,
-                            [] { ipm64::cbar(); });
+                            [] { ipm::cbar(); });
         if (n <= -3 && A.app_list && olane() == 0) {  // append to the bigger class's list
           const int cls = -3 - n <= 128 ? 1 : 2;
           const int pos = atomicAdd(&A.app_count[cls], 1);
@@ -503,37 +426,16 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
 #else
     const bool st_on = A.stats && it < A.stats_cap;  // statistics row of this iteration (cmpc_enable_stats)
 #endif
-    auto st_row = [&]() { return A.stats + ((size_t)q * A.stats_cap + it) * CMPC_STAT_COLS; };
+    auto st_row = [&]() { return stat_row(A, q, it); };
     if (st_on) {  // statistics row of this iteration: residuals and mu now, the step below (NaN if none is taken)
       const T r0 = wave_max_dpp(rs), r1 = wave_max_dpp(ri), r2 = wave_max_dpp(rc);
-      if (lane == 0) {
-        double* sr = st_row();
-        for (int k = 0; k < 5; ++k) sr[k] = __builtin_nan("");
-        sr[5] = (double)mu;
-        sr[6] = (double)r0;
-        sr[7] = 0.0;
-        sr[8] = (double)r1;
-        sr[9] = (double)r2;
-      }
+      if (lane == 0) stat_open(st_row(), mu, r0, r1, r2);
     }
-    // a non-finite residual anywhere -> NAN_SOL; HPIPM's absolute stopping rule (tol_stat / tol_ineq / tol_comp)
-    // as a wave vote: max over lanes <= tol iff every lane <= tol (no max-reductions needed)
-    if (__any(!(isfinite(rs) && isfinite(ri) && isfinite(rc)))) {
-      status = CMPC_NAN_SOL;
-      break;
-    }
-    if (__all(rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp))) {
-      status = CMPC_SUCCESS;
-      break;
-    }
-    if (it >= S.iter_max) {
-      status = CMPC_MAX_ITER;
-      break;
-    }
-    if (uflag(m > 0 && !(mu > T(Lim<T>::mu_min)))) {
-      status = CMPC_MIN_STEP;
-      break;
-    }
+    // stopping rule (ipm_common.hpp: IPM_BREAK_IF_STOPPED) as wave votes: max over lanes <= tol iff every lane <= tol
+    // (no max-reductions needed)
+    IPM_BREAK_IF_STOPPED(status, __any(!(isfinite(rs) && isfinite(ri) && isfinite(rc))),
+                         __all(rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp)), it, S.iter_max,
+                         uflag(m > 0 && !(mu > T(Lim<T>::mu_min))));
     IPM_STAMP(0);
 
     // ---- Newton matrix K = H + C' diag(lam_l/t_l + lam_u/t_u) C + reg I: lane j writes the 3x3 block row of
@@ -715,14 +617,8 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
         maff += on ? v : T(0);
       }
       maff = wave_sum_dpp(maff) / T(2 * m);
-      const T ratio = maff / mu;
-      const T sigma = ratio * ratio * ratio;
-      if (st_on && lane == 0) {
-        double* sr = st_row();
-        sr[0] = (double)alpha;
-        sr[1] = (double)maff;
-        sr[2] = (double)sigma;
-      }
+      const T sigma = centering(maff, mu);
+      if (st_on && lane == 0) stat_predictor(st_row(), alpha, maff, sigma);
       IPM_STAMP(5);
       // ---- corrector: rm = t.lam + dt_aff.dlam_aff - sigma mu
 #pragma unroll
@@ -738,10 +634,7 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
       alpha = fmin(T(1), max_step());
     }
     IPM_STAMP(6);
-    if (st_on && lane == 0) {
-      double* sr = st_row();
-      sr[3] = sr[4] = (double)alpha;
-    }  // one step length for primal and dual
+    if (st_on && lane == 0) stat_step(st_row(), alpha);
     if (uflag(alpha < T(S.alpha_min))) {
       status = CMPC_MIN_STEP;
       break;
@@ -780,25 +673,16 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
   if (A.res) {  // max over the lanes of the last residual terms (the same lanes stored them)
     const T* rp = A.res_scr + (size_t)q * 3 * 64 + lane;
     const T r0 = wave_max_dpp(rp[0]), r1 = wave_max_dpp(rp[64]), r2 = wave_max_dpp(rp[128]);
-    if (lane == 0) {
-      double* o = A.res + (size_t)q * 4;
-      o[0] = (double)r0;
-      o[1] = 0.0;
-      o[2] = (double)r1;
-      o[3] = (double)r2;
-    }
+    if (lane == 0) res_store(A.res, q, r0, r1, r2);
   }
-  IPM_STAMP_STORE(A.stamps, q);
+  IPM_STAMP_STORE(A.stamps, q, 8, 9);
+  IPM64_TIMELINE_STORE(A.stamps, q);
 }
 
 template <typename T, int WPE>
 __global__ __launch_bounds__(64, WPE) void k_ipm64(IpmArgs<T> A) {
-  int q = blockIdx.x;
-  if (A.qlist[0]) {  // compacted class list: real QPs first, the surplus workgroups exit
-    if (q >= A.qcount[0]) return;
-    q = A.qlist[0][q];
-    if ((unsigned)q >= gridDim.x) return;  // grid = batch: a corrupt list entry cannot address past it
-  }
+  int q;
+  if (!ipm::class_qp(A, 0, q)) return;
   ipm64_body<T, WPE, 0>(A, nullptr, q);
 }
 

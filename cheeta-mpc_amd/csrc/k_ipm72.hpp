@@ -24,7 +24,8 @@
 namespace cmpc {
 
 // Lab instrumentation (-DCMPC_IPM72_STAMPS, lab/ipm72_stamps.sh only, never in libcmpc.so): per-wave shader-clock
-// cycles per phase, summed over every QP into ipm72_stamp_acc (read by cmpc_ipm72_debug_stamps). Phases: 0 H +
+// cycles per phase, summed over every QP into ipm72_stamp_acc (read by cmpc_ipm72_debug_stamps). Local to this kernel,
+// not the IPM_STAMP* trio of ipm_common.hpp: one global accumulator by atomics instead of a row per QP. Phases: 0 H +
 // residuals, 1 Newton blocks, 2 LDL' of K_AA, 3 Y = M K_AB, 4 S, 5 S^-1, 6 predictor, 7 corrector, 8 update,
 // 9 iterations, 10 total.
 #ifdef CMPC_IPM72_STAMPS
@@ -100,7 +101,7 @@ __device__ __forceinline__ T row_reduce_scatter16(const T (&p)[16], int b) {
 template <typename T, int WPE>
 __device__ __forceinline__ void ipm72_body(const IpmArgs<T>& A, int q) {
   __shared__ ipm72::Lds72<T> L;
-  using namespace ipm64;
+  using namespace ipm;
   constexpr int NP = ipm72::NP, NB = ipm72::NB;
   T K[64];
   if (A.status[q] != CMPC_SUCCESS) return;
@@ -393,35 +394,15 @@ __device__ __forceinline__ void ipm72_body(const IpmArgs<T>& A, int q) {
     ms = wave_sum_dpp(ms);
     const T mu = m > 0 ? ms / T(2 * m) : T(0);
     const bool st_on = A.stats && it < A.stats_cap;
-    auto st_row = [&]() { return A.stats + ((size_t)q * A.stats_cap + it) * CMPC_STAT_COLS; };
+    auto st_row = [&]() { return stat_row(A, q, it); };
     if (st_on) {
       const T r0 = wave_max_dpp(rs), r1 = wave_max_dpp(ri), r2 = wave_max_dpp(rc);
-      if (lane == 0) {
-        double* sr = st_row();
-        for (int k = 0; k < 5; ++k) sr[k] = __builtin_nan("");
-        sr[5] = (double)mu;
-        sr[6] = (double)r0;
-        sr[7] = 0.0;
-        sr[8] = (double)r1;
-        sr[9] = (double)r2;
-      }
+      if (lane == 0) stat_open(st_row(), mu, r0, r1, r2);
     }
-    if (__any(!(isfinite(rs) && isfinite(ri) && isfinite(rc)))) {
-      status = CMPC_NAN_SOL;
-      break;
-    }
-    if (__all(rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp))) {
-      status = CMPC_SUCCESS;
-      break;
-    }
-    if (it >= S.iter_max) {
-      status = CMPC_MAX_ITER;
-      break;
-    }
-    if (uflag(m > 0 && !(mu > T(Lim<T>::mu_min)))) {
-      status = CMPC_MIN_STEP;
-      break;
-    }
+    // stopping rule (ipm_common.hpp: IPM_BREAK_IF_STOPPED) as wave votes
+    IPM_BREAK_IF_STOPPED(status, __any(!(isfinite(rs) && isfinite(ri) && isfinite(rc))),
+                         __all(rs <= T(S.tol_stat) && ri <= T(S.tol_ineq) && rc <= T(S.tol_comp)), it, S.iter_max,
+                         uflag(m > 0 && !(mu > T(Lim<T>::mu_min))));
 
     I72(0);
     // ---- Newton matrix K = H + C' diag(lam_l/t_l + lam_u/t_u) C + reg I: 3x3 block rows of both slots
@@ -686,14 +667,8 @@ __device__ __forceinline__ void ipm72_body(const IpmArgs<T>& A, int q) {
         maff += on ? v : T(0);
       }
       maff = wave_sum_dpp(maff) / T(2 * m);
-      const T ratio = maff / mu;
-      const T sigma = ratio * ratio * ratio;
-      if (st_on && lane == 0) {
-        double* sr = st_row();
-        sr[0] = (double)alpha;
-        sr[1] = (double)maff;
-        sr[2] = (double)sigma;
-      }
+      const T sigma = centering(maff, mu);
+      if (st_on && lane == 0) stat_predictor(st_row(), alpha, maff, sigma);
       I72(6);
       // ---- corrector: rm = t.lam + dt_aff.dlam_aff - sigma mu
 #pragma unroll
@@ -708,10 +683,7 @@ __device__ __forceinline__ void ipm72_body(const IpmArgs<T>& A, int q) {
     } else {
       alpha = fmin(T(1), max_step());
     }
-    if (st_on && lane == 0) {
-      double* sr = st_row();
-      sr[3] = sr[4] = (double)alpha;
-    }
+    if (st_on && lane == 0) stat_step(st_row(), alpha);
     I72(7);
     if (uflag(alpha < T(S.alpha_min))) {
       status = CMPC_MIN_STEP;
@@ -775,25 +747,15 @@ __device__ __forceinline__ void ipm72_body(const IpmArgs<T>& A, int q) {
   if (A.res) {
     const T* rp = A.res_scr + (size_t)q * 3 * 64 + lane;
     const T r0 = wave_max_dpp(rp[0]), r1 = wave_max_dpp(rp[64]), r2 = wave_max_dpp(rp[128]);
-    if (lane == 0) {
-      double* o = A.res + (size_t)q * 4;
-      o[0] = (double)r0;
-      o[1] = 0.0;
-      o[2] = (double)r1;
-      o[3] = (double)r2;
-    }
+    if (lane == 0) res_store(A.res, q, r0, r1, r2);
   }
 }
 
 // One wave per QP of its list (run_ipm_classes splits 64 < n <= 72 off the 128 class: qlist[1] / qcount[1] here)
 template <typename T, int WPE>
 __global__ __launch_bounds__(64, WPE) void k_ipm72(IpmArgs<T> A) {
-  int q = blockIdx.x;
-  if (A.qlist[1]) {
-    if (q >= A.qcount[1]) return;
-    q = A.qlist[1][q];
-    if ((unsigned)q >= gridDim.x) return;
-  }
+  int q;
+  if (!ipm::class_qp(A, 1, q)) return;
   ipm72_body<T, WPE>(A, q);
 }
 

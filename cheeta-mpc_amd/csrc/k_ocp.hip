@@ -22,6 +22,7 @@
 
 #include <algorithm>
 
+#include "ipm_common.hpp"
 #include "k_ocp.hpp"
 
 namespace cmpc {
@@ -30,6 +31,8 @@ namespace {
 constexpr int NT = OCP_NT;
 typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr double TAU_OCP = 0.995;  // fraction-to-boundary, as oracle/ocp_ipm.c
+// the dense IPM's guards (ipm_common.hpp; restated in oracle/ocp_ipm.c), also for ocp_chain.hpp and ocp_part.hpp
+constexpr double PIVOT_MIN = ipm::Lim<double>::pivot_min, MU_MIN = ipm::Lim<double>::mu_min;
 
 // Lab instrumentation (-DCMPC_OCP_STAMPS, lab/ocp_stamps.sh only, never in libcmpc.so): thread 0 of problem 0
 // accumulates shader-clock cycles per phase (s_memtime) into a device array read by cmpc_ocp_debug_stamps.
@@ -851,7 +854,7 @@ __device__ __forceinline__ bool factor_pass(const View& V, const Lds& S, double 
         const double* c1 = c0 + NZP;
         const double d0 = c0[j];
         bad = bad || (d0 != d0);
-        const double dinv0 = d0 > 1e-200 ? 1.0 / d0 : 0.0;
+        const double dinv0 = d0 > PIVOT_MIN ? 1.0 / d0 : 0.0;
         // the pivot columns of the Schur complement are the columns of L D (the LDL' factor of M_uu), rows p..mk-1
         if (tid >= j && tid < mk) Lf[(long long)j * mk + tid] = c0[tid];
         if (j + 1 < mk) {
@@ -872,7 +875,7 @@ __device__ __forceinline__ bool factor_pass(const View& V, const Lds& S, double 
           }
           const double d1 = fma(-a1 * dinv0, a1, c1[j + 1]);
           bad = bad || (d1 != d1);
-          const double dinv1 = d1 > 1e-200 ? 1.0 / d1 : 0.0;
+          const double dinv1 = d1 > PIVOT_MIN ? 1.0 / d1 : 0.0;
           if (tid > j && tid < mk) {
             const double at = c0[tid];
             Lf[(long long)(j + 1) * mk + tid] = fma(-at * dinv0, a1, c1[tid]);
@@ -1155,14 +1158,14 @@ __device__ __forceinline__ void ldl_solve(const double* __restrict__ F, int m, c
   for (int i = 0; i < m; ++i) x[i] = z[i];
   for (int j = 0; j < m; ++j) {  // L D y = z, then y /= d
     const double d = F[(long long)j * m + j];
-    const double dinv = d > 1e-200 ? 1.0 / d : 0.0;
+    const double dinv = d > PIVOT_MIN ? 1.0 / d : 0.0;
     const double yj = x[j] * dinv;
     for (int i = j + 1; i < m; ++i) x[i] = fma(-F[(long long)j * m + i], yj, x[i]);
     x[j] = yj;
   }
   for (int j = m - 1; j >= 0; --j) {  // L' x = y
     const double d = F[(long long)j * m + j];
-    const double dinv = d > 1e-200 ? 1.0 / d : 0.0;
+    const double dinv = d > PIVOT_MIN ? 1.0 / d : 0.0;
     double s = x[j];
     for (int i = j + 1; i < m; ++i) s = fma(-F[(long long)j * m + i] * dinv, x[i], s);
     x[j] = s;
@@ -1577,7 +1580,7 @@ __device__ __forceinline__ void ipm_body(const OcpSolveArgs& a, int q, const Lds
       status = 1;
       break;
     }
-    if (m > 0 && !(mu > 1e-300)) {
+    if (m > 0 && !(mu > MU_MIN)) {
       status = 2;
       break;
     }
@@ -2101,7 +2104,7 @@ __device__ __forceinline__ void ipm_grid(const OcpSolveArgs& a, int q, int g, co
     if (!(isfinite(rs) && isfinite(re) && isfinite(ri) && isfinite(rc))) ex = 3;
     else if (rs <= a.tol_stat && re <= a.tol_eq && ri <= a.tol_ineq && rc <= a.tol_comp) ex = 0;
     else if (it >= a.iter_max) ex = 1;
-    else if (m > 0 && !(mu > 1e-300)) ex = 2;
+    else if (m > 0 && !(mu > MU_MIN)) ex = 2;
     if (ex >= 0) {
       status = ex;
       // the exit point's factorisation for keep_riccati: with rows at the exit point's Sigma; without rows the last
@@ -2282,7 +2285,7 @@ __device__ __forceinline__ void ipm_grid(const OcpSolveArgs& a, int q, int g, co
         for (int e = tid; e < mk * mk; e += NT) {
           const int j = e / mk, i = e - j * mk;
           const double d = F[(long long)j * mk + j];
-          Lo[e] = (i >= j && d > 1e-200) ? F[e] / sqrt(d) : 0.0;
+          Lo[e] = (i >= j && d > PIVOT_MIN) ? F[e] / sqrt(d) : 0.0;
         }
       }
       for (int e = (R.k0 > 1 ? L.cu[R.k0] : L.cu[1]) + tid; !fonly && e < R.u1; e += NT) {
@@ -2430,7 +2433,7 @@ __device__ __forceinline__ void ric_body(const OcpRicArgs& r, int q, const Lds& 
     for (int e = tid; e < mk * mk; e += NT) {
       const int j = e / mk, i = e % mk;
       const double d = F[(long long)j * mk + j];
-      Lo[e] = (i >= j && d > 1e-200) ? F[e] / sqrt(d) : 0.0;
+      Lo[e] = (i >= j && d > PIVOT_MIN) ? F[e] / sqrt(d) : 0.0;
     }
   }
   for (int it = tid; it < L.nU; it += NT) {

@@ -34,21 +34,15 @@
 #include "cmpc_kernels.hpp"
 #include "step_ratio.hpp"
 #include "wave_dpp.hpp"
+#include "ipm_common.hpp"
 
-// Diagnostic builds only (-DCMPC_RIC_STAMPS, lab): s_memtime cycles per phase of each QP, written over row 0 of the
-// statistics buffer (cmpc_enable_stats): [0] setup, [1] gradient, [2] factorisations, [3] solves, [4] the rest of the
+// Diagnostic builds only (-DCMPC_RIC_STAMPS, lab): s_memtime cycles per phase of each QP (the stamp macros of
+// ipm_common.hpp under this kernel's own switch), written over row 0 of the statistics buffer (cmpc_enable_stats) by
+// a store local to this kernel: [0] setup, [1] gradient, [2] factorisations, [3] solves, [4] the rest of the
 // iterations, [5] total, [6] iterations.
 #ifdef CMPC_RIC_STAMPS
-#define RIC_STAMP_DECL                                 \
-  unsigned long long rst_[6] = {0, 0, 0, 0, 0, 0};    \
-  const unsigned long long rst0_ = ric::memtime();    \
-  unsigned long long rprev_ = rst0_
-#define RIC_STAMP(k)                             \
-  do {                                           \
-    const unsigned long long t_ = ric::memtime(); \
-    rst_[k] += t_ - rprev_;                      \
-    rprev_ = t_;                                 \
-  } while (0)
+#define RIC_STAMP_DECL IPM_STAMP_DECL_ON(5)
+#define RIC_STAMP(k) IPM_STAMP_ON(k)
 #else
 #define RIC_STAMP_DECL (void)0
 #define RIC_STAMP(k) (void)0
@@ -58,29 +52,10 @@ namespace cmpc {
 
 namespace ric {
 
-__device__ __forceinline__ unsigned long long memtime() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
+// The lanes of the one wave exchange through LDS behind ipm::wave_sync(). The factor store and every exchange live in
+// LDS, so its fence has no outstanding global stores to wait for inside the iteration.
 constexpr int ZS = 24;           // z slots: 12 state rows + 12 previous-force slots
 constexpr int RS = 12 * 12 + 12 * ZS;  // scratch per stage: Li [12][12], Y [12][24]
-
-template <typename T>
-struct Lim;
-template <>
-struct Lim<double> {
-  static constexpr double pivot_min = 1e-200;
-  static constexpr double mu_min = 1e-300;
-};
-template <>
-struct Lim<float> {
-  static constexpr float pivot_min = 1e-30f;
-  static constexpr float mu_min = 1e-35f;
-};
 
 template <typename T, int NR, int TPL, int FS>
 struct Lds {
@@ -113,15 +88,6 @@ struct Lds {
   };
 };
 
-// Ordering of LDS traffic between the lanes of the one wave (the workgroup is one wave): LDS writes drained
-// (lgkmcnt) before the other lanes read them. The factor store and every exchange live in LDS, so the fence has no
-// outstanding global stores to wait for inside the iteration.
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 template <typename T>
 __device__ __forceinline__ T shfl_x32(T v) {
   return __shfl_xor(v, 32, 64);
@@ -132,7 +98,7 @@ __device__ __forceinline__ int cslot(int sk, int a) { return 3 * __popc(sk & ((1
 
 template <typename T>
 __device__ __forceinline__ T pinv_sqrt(T d) {
-  return d > T(Lim<T>::pivot_min) ? T(rsqrt_acc(d)) : T(0);
+  return d > T(ipm::Lim<T>::pivot_min) ? T(rsqrt_acc(d)) : T(0);
 }
 
 }  // namespace ric
@@ -140,6 +106,7 @@ __device__ __forceinline__ T pinv_sqrt(T d) {
 // Body of one QP. TPL: force triples per lane (nt <= 64 TPL); NR: longest horizon the LDS block holds.
 template <typename T, int TPL, int NR, int FS>
 __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
+  using namespace ipm;
   using namespace ric;
   __shared__ Lds<T, NR, TPL, FS> S;
   const DevModel* __restrict__ M = A.model;
@@ -213,7 +180,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
     S.wf2[lane] = T(2.0 * M->Wf[lane]);
     S.wr2[lane] = T(2.0 * M->Wr[lane]);
   }
-  wsync();
+  wave_sync();
   // triple table, lever arms (stance_point, cmpc_device.hpp) and the Theta rows of A_k
   for (int e = lane; e < NL * N; e += 64) {
     const int k = e >> 2, l = e & 3;
@@ -244,7 +211,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         S.Mth[lane][r * 3 + c] = M->dt * s;
       }
   }
-  wsync();
+  wave_sync();
 
   // ---- lane-per-triple data
   int tkv[TPL], tlv[TPL];
@@ -286,7 +253,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
   T hug[TPL][3];
   {
     for (int e = lane; e < N * 12; e += 64) S.g.uf[e / 12][e % 12] = T(0);
-    wsync();
+    wave_sync();
 #pragma unroll
     for (int c = 0; c < TPL; ++c)
       if (ton[c])
@@ -297,7 +264,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
     const double dtd = M->dt, dtmd = M->dt_over_m;
     for (int k = 0; k < N; ++k) {
       if (lane < 16) S.g.X[k][lane] = lane < NX ? xs : 0.0;
-      wsync();
+      wave_sync();
       if (lane < NX) {
         const int s = lane;
         const double* X = S.g.X[k];
@@ -333,18 +300,18 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
         xs = xn;
       }
-      wsync();
+      wave_sync();
     }
     if (lane < 16) S.g.X[N][lane] = lane < NX ? xs : 0.0;
-    wsync();
+    wave_sync();
     // adjoint: lambda_N = qdiag_N (X_N - xref_N); lambda_k = qdiag_k (X_k - xref_k) + A_k' lambda_{k+1}; slot k + 1
     // of S.g.X is overwritten with lambda_{k+1} once X_{k+1} has been used
     double lam = lane < NX ? M->qdiag[N][lane] * (xs - xrq[N * NX + lane]) : 0.0;
     for (int k = N - 1; k >= 0; --k) {
       const double xk = lane < NX ? S.g.X[k][lane] : 0.0;
-      wsync();
+      wave_sync();
       if (lane < 16) S.g.X[k + 1][lane] = lane < NX ? lam : 0.0;
-      wsync();
+      wave_sync();
       if (k > 0 && lane < NX) {
         const double* Lm = S.g.X[k + 1];
         const int s = lane;
@@ -365,7 +332,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         lam = ln;
       }
     }
-    wsync();
+    wave_sync();
     // gradient of each triple: B_k' lambda_{k+1} + 2 Wf (u - f_des) + force-rate terms
 #pragma unroll
     for (int c = 0; c < TPL; ++c) {
@@ -391,7 +358,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
       }
     }
-    wsync();
+    wave_sync();
   }
 
   RIC_STAMP(1);
@@ -452,7 +419,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
           }
         }
       }
-      wsync();
+      wave_sync();
       // 2. Rt = R_k + G B~: lane (slot a, leg b) forms Rt[a][3b .. 3b + 2]
       if (lane < 48) {
         const int a = lane % 12, lb = lane / 12;
@@ -478,7 +445,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
           }
         }
       }
-      wsync();
+      wave_sync();
       // 3. Cholesky Rt = L L' and Li = L^-1, lane a < 12 holds row a
       {
         T R[12], Iv[12];
@@ -512,7 +479,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
       }
       if (k == 0) break;
-      wsync();
+      wave_sync();
       // 4. St = S_k + G A~ (column jj of z_k), Y = Li St
       T Yc[12];
       {
@@ -554,7 +521,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         for (int a = 0; a < 12; ++a)
           if ((Sk >> (a / 3)) & 1) Yx[cslot(Sk, a) * 12 + jj] = Yc[a];
       }
-      wsync();
+      wave_sync();
       // 5. P_k = Q_k + A~' P A~ - Y' Y (+ 2 Wr on the previous-force slots of the legs of step k - 1)
       T nc[12];
       if (hh == 0 && jj < 12) {
@@ -603,9 +570,9 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
       }
 #pragma unroll
       for (int r = 0; r < 12; ++r) Pc[r] = colv ? nc[r] : T(0);
-      wsync();
+      wave_sync();
     }
-    wsync();
+    wave_sync();
     return !__any(nanp);
   };
 
@@ -627,7 +594,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
       const T* F = S.fac + S.foff[k];
       const T* Yx = F + m * (m + 1) / 2;
       if (lane < ZS) S.vec[lane] = pv;
-      wsync();
+      wave_sync();
       T hva = T(0);
       const bool sa = lane < 12 && ((Sk >> (lane / 3)) & 1);
       const int ap = sa ? cslot(Sk, lane) : 0;
@@ -642,7 +609,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
               S.vec[12 + lane];
       }
       if (lane < 12) S.hv[lane] = hva;
-      wsync();
+      wave_sync();
       T wa = T(0);
       if (sa) {
         const T* Lr = F + ap * (ap + 1) / 2;
@@ -653,7 +620,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
       }
       if (k == 0) break;
       if (lane < 12) S.hv2[lane] = wa;
-      wsync();
+      wave_sync();
       if (lane < ZS) {
         T v = T(0);
         if (lane < 12) {
@@ -683,9 +650,9 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
         pv = v;
       }
-      wsync();
+      wave_sync();
     }
-    wsync();
+    wave_sync();
     // forward sweep
     T zv = T(0);
     for (int k = 0; k < N; ++k) {
@@ -696,7 +663,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
       const T* F = S.fac + S.foff[k];
       const T* Yx = F + m * (m + 1) / 2;
       if (lane < ZS) S.vec[lane] = zv;
-      wsync();
+      wave_sync();
       const bool sa = lane < 12 && ((Sk >> (lane / 3)) & 1);
       const int ap = sa ? cslot(Sk, lane) : 0;
       T ya = T(0);
@@ -713,7 +680,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
       }
       if (lane < 12) S.hv[lane] = ya;
-      wsync();
+      wave_sync();
       T va = T(0);
       if (sa) {
 #pragma unroll
@@ -727,7 +694,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         S.bs[3 * t + d] = va;
       }
       if (lane < 12) S.hv2[lane] = va;
-      wsync();
+      wave_sync();
       if (lane < ZS && k + 1 < N) {
         T v;
         if (lane < 12) {
@@ -761,7 +728,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         }
         zv = v;
       }
-      wsync();
+      wave_sync();
     }
 #pragma unroll
     for (int c = 0; c < TPL; ++c)
@@ -770,7 +737,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) bx[c][d] = S.bs[3 * t + d];
       }
-    wsync();
+    wave_sync();
   };
 
   int status = CMPC_MAX_ITER;
@@ -859,35 +826,15 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
     ms = wave_sum_dpp(ms);
     const T mu = m > 0 ? ms / T(2 * m) : T(0);
     const bool st_on = A.stats && it < A.stats_cap;
-    auto st_row = [&]() { return A.stats + ((size_t)q * A.stats_cap + it) * CMPC_STAT_COLS; };
+    auto st_row = [&]() { return stat_row(A, q, it); };
     if (st_on) {
       const T r0 = wave_max_dpp(rs), r1 = wave_max_dpp(ri), r2 = wave_max_dpp(rc);
-      if (lane == 0) {
-        double* sr = st_row();
-        for (int k = 0; k < 5; ++k) sr[k] = __builtin_nan("");
-        sr[5] = (double)mu;
-        sr[6] = (double)r0;
-        sr[7] = 0.0;
-        sr[8] = (double)r1;
-        sr[9] = (double)r2;
-      }
+      if (lane == 0) stat_open(st_row(), mu, r0, r1, r2);
     }
-    if (__any(!(isfinite(rs) && isfinite(ri) && isfinite(rc)))) {
-      status = CMPC_NAN_SOL;
-      break;
-    }
-    if (__all(rs <= T(st.tol_stat) && ri <= T(st.tol_ineq) && rc <= T(st.tol_comp))) {
-      status = CMPC_SUCCESS;
-      break;
-    }
-    if (it >= st.iter_max) {
-      status = CMPC_MAX_ITER;
-      break;
-    }
-    if (m > 0 && !(mu > T(Lim<T>::mu_min))) {
-      status = CMPC_MIN_STEP;
-      break;
-    }
+    // stopping rule (ipm_common.hpp: IPM_BREAK_IF_STOPPED) as wave votes
+    IPM_BREAK_IF_STOPPED(status, __any(!(isfinite(rs) && isfinite(ri) && isfinite(rc))),
+                         __all(rs <= T(st.tol_stat) && ri <= T(st.tol_ineq) && rc <= T(st.tol_comp)), it, st.iter_max,
+                         m > 0 && !(mu > T(Lim<T>::mu_min)));
     // ---- Newton blocks C' diag(lam_l / t_l + lam_u / t_u) C + reg I of every triple
 #pragma unroll
     for (int c = 0; c < TPL; ++c) {
@@ -911,7 +858,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
         bk[4] = mv * (sg[3] - sg[2]);
       }
     }
-    wsync();
+    wave_sync();
     RIC_STAMP(4);
     if (!factor()) {
       status = CMPC_NAN_SOL;
@@ -950,14 +897,8 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
             maff += (tl[c][r] + alpha * dtl[c][r]) * (ll[c][r] + alpha * dll[c][r]) +
                     (tu[c][r] + alpha * dtu[c][r]) * (lu[c][r] + alpha * dlu[c][r]);
       maff = wave_sum_dpp(maff) / T(2 * m);
-      const T ratio = maff / mu;
-      const T sigma = ratio * ratio * ratio;
-      if (st_on && lane == 0) {
-        double* sr = st_row();
-        sr[0] = (double)alpha;
-        sr[1] = (double)maff;
-        sr[2] = (double)sigma;
-      }
+      const T sigma = centering(maff, mu);
+      if (st_on && lane == 0) stat_predictor(st_row(), alpha, maff, sigma);
       // ---- corrector
 #pragma unroll
       for (int c = 0; c < TPL; ++c)
@@ -971,10 +912,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
     } else {
       alpha = fmin(T(1), max_step());
     }
-    if (st_on && lane == 0) {
-      double* sr = st_row();
-      sr[3] = sr[4] = (double)alpha;
-    }
+    if (st_on && lane == 0) stat_step(st_row(), alpha);
     if (alpha < T(st.alpha_min)) {
       status = CMPC_MIN_STEP;
       break;
@@ -1008,8 +946,8 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
 #ifdef CMPC_RIC_STAMPS
   if (A.stats && lane == 0) {
     double* o = A.stats + (size_t)q * A.stats_cap * CMPC_STAT_COLS;
-    for (int k = 0; k < 5; ++k) o[k] = (double)rst_[k];
-    o[5] = (double)(ric::memtime() - rst0_);
+    for (int k = 0; k < 5; ++k) o[k] = (double)st_acc_[k];
+    o[5] = (double)(memtime() - st_t0_);
     o[6] = (double)it;
   }
 #endif
@@ -1035,19 +973,13 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
   }
   if (A.res) {
     const T r0 = wave_max_dpp(rs_last), r1 = wave_max_dpp(ri_last), r2 = wave_max_dpp(rc_last);
-    if (lane == 0) {
-      double* o = A.res + (size_t)q * 4;
-      o[0] = (double)r0;
-      o[1] = 0.0;
-      o[2] = (double)r1;
-      o[3] = (double)r2;
-    }
+    if (lane == 0) res_store(A.res, q, r0, r1, r2);
   }
   if (A.out_u) {
     double* uo = A.out_u + (size_t)q * A.out_nu;
     for (int p = lane; p < A.out_nu; p += 64) uo[p] = 0.0;
     __threadfence_block();
-    wsync();
+    wave_sync();
 #pragma unroll
     for (int c = 0; c < TPL; ++c)
       if (ton[c])
@@ -1063,6 +995,7 @@ __device__ __forceinline__ void ric_body(const RicArgs<T>& A, const int q) {
 template <typename T, int TPL, int NR, int FS, int WPE>
 __global__ __launch_bounds__(64, WPE) void k_ric(RicArgs<T> A) {
   int q = (int)blockIdx.x;
+  // not ipm::class_qp: RicArgs carries two lists served back to back by one grid
   if (A.qlist) {  // class lists of the fused path: list 1 then list 2; the surplus workgroups exit
     const int c1 = A.qcount[0], c2 = A.qlist2 ? A.qcount[1] : 0;
     if (q < c1) q = A.qlist[q];

@@ -291,12 +291,12 @@ __device__ __forceinline__ void chain_round(double (&m)[NB][4][4], const int (&b
   __builtin_amdgcn_wave_barrier();
   const double d0 = c0[j], a1 = c0[j1], e1 = c1[j1];
   bad = bad || (d0 != d0);
-  const double d0i = d0 > 1e-200 ? 1.0 / d0 : 0.0;
+  const double d0i = d0 > PIVOT_MIN ? 1.0 / d0 : 0.0;
   const double l1 = a1 * d0i;
   const double d1 = fma(-a1, l1, e1);
   bad = bad || (two && d1 != d1);
-  const double d1i = (two && d1 > 1e-200) ? 1.0 / d1 : 0.0;
-  if (WEAK) weak = weak || !(d0 > 1e-200) || (two && !(d1 > 1e-200));
+  const double d1i = (two && d1 > PIVOT_MIN) ? 1.0 / d1 : 0.0;
+  if (WEAK) weak = weak || !(d0 > PIVOT_MIN) || (two && !(d1 > PIVOT_MIN));
   // the factor's columns into the F image (rows >= j; chain_out reads column j + 1 from row j + 1)
   if (lane >= j && lane < n1) {
     const double v0 = c0[lane];
@@ -361,11 +361,11 @@ __device__ __forceinline__ void chain_round4(double (&m)[NB][4][4], const int (&
   // first pair, as chain_round
   const double d0 = q0a.x, a1 = q0a.y, e1 = q1b.y;
   bad = bad || (d0 != d0);
-  const double d0i = d0 > 1e-200 ? 1.0 / d0 : 0.0;
+  const double d0i = d0 > PIVOT_MIN ? 1.0 / d0 : 0.0;
   const double l1 = a1 * d0i;
   const double d1 = fma(-a1, l1, e1);
   bad = bad || (d1 != d1);
-  const double d1i = d1 > 1e-200 ? 1.0 / d1 : 0.0;
+  const double d1i = d1 > PIVOT_MIN ? 1.0 / d1 : 0.0;
   // the first pair's row / column vectors at index y (published pre-round values c0_y, c1_y)
   auto u_of = [&](double x0) { return -x0 * d0i; };
   auto p_of = [&](double x0, double x1) { return fma(-x0, l1, x1); };
@@ -378,12 +378,12 @@ __device__ __forceinline__ void chain_round4(double (&m)[NB][4][4], const int (&
   const double a3 = fma(v3, bl2, fma(u3, cl2, q2b.y));  // M'(j+3, j+2)
   const double e3 = fma(v3, bl3, fma(u3, cl3, q3b.y));  // M'(j+3, j+3)
   bad = bad || (e2 != e2);
-  const double d2i = e2 > 1e-200 ? 1.0 / e2 : 0.0;
+  const double d2i = e2 > PIVOT_MIN ? 1.0 / e2 : 0.0;
   const double l3 = a3 * d2i;
   const double d3 = fma(-a3, l3, e3);
   bad = bad || (d3 != d3);
-  const double d3i = d3 > 1e-200 ? 1.0 / d3 : 0.0;
-  if (WEAK) weak = weak || !(d0 > 1e-200) || !(d1 > 1e-200) || !(e2 > 1e-200) || !(d3 > 1e-200);
+  const double d3i = d3 > PIVOT_MIN ? 1.0 / d3 : 0.0;
+  if (WEAK) weak = weak || !(d0 > PIVOT_MIN) || !(d1 > PIVOT_MIN) || !(e2 > PIVOT_MIN) || !(d3 > PIVOT_MIN);
   // the factor's columns j .. j + 3 (rows >= j): c0, c1~, the updated column j + 2 and its c~ for j + 3
   if (lane >= j && lane < n1) {
     const double x0 = c0[lane], x1 = c1[lane], x2 = c2[lane], x3 = c3[lane];
@@ -562,7 +562,7 @@ __device__ __forceinline__ void chain_gains(const View& V, int k0, int k1) {
     double* x = c < nx ? V.K(k) + c * mk : V.kf() + L.cu[k];
     for (int a = mk - 1; a >= 0; --a) {
       const double da = F[a * mk + a];
-      const double dai = da > 1e-200 ? 1.0 / da : 0.0;
+      const double dai = da > PIVOT_MIN ? 1.0 / da : 0.0;
       double s = x[a];
       for (int b = a + 1; b < mk; ++b) s = fma(F[a * mk + b], x[b], s);
       x[a] = -(s * dai);

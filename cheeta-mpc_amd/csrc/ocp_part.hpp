@@ -230,7 +230,7 @@ __device__ __forceinline__ int seg_element(const View& V, const ChainLds& CS, in
             if (c0 + u < q) s2 = fma(-fq[u], yc[u], s2);
         }
         const double d = F[q * mk + q];
-        Yd[q * nx + r] = d > 1e-200 ? s2 / d : 0.0;
+        Yd[q * nx + r] = d > PIVOT_MIN ? s2 / d : 0.0;
       }
     }
     __syncthreads();
@@ -279,7 +279,7 @@ __device__ __forceinline__ int seg_element(const View& V, const ChainLds& CS, in
           const int r0 = 16 * (w % nt), c0 = 16 * (w / nt), j = c0 + lr;
           const v4d acc = mtile(Ph, 1, nx, X, 1, nx, r0, c0, nx, LX, nx, v4d{0.0, 0.0, 0.0, 0.0});
           const int qd = (j >= nx && j < nx + mk) ? j - nx : 0;
-          const double d = F[qd * mk + qd], sd = d > 1e-200 ? sqrt(d) : 0.0;
+          const double d = F[qd * mk + qd], sd = d > PIVOT_MIN ? sqrt(d) : 0.0;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int i = r0 + lk + 4 * q;
@@ -353,7 +353,7 @@ __device__ __forceinline__ int seg_element(const View& V, const ChainLds& CS, in
     if (e < nxx) {
       const int x = e % nx, j = e / nx;
       const double d = CS.F0[j * CH_FS + j];
-      v = (x >= j && d > 1e-200) ? CS.F0[j * CH_FS + x] / sqrt(d) : 0.0;
+      v = (x >= j && d > PIVOT_MIN) ? CS.F0[j * CH_FS + x] / sqrt(d) : 0.0;
     } else if (e < 2 * nxx + nx) {
       v = e < 2 * nxx ? Ph[e - nxx] : fv[e - 2 * nxx];
     } else {
