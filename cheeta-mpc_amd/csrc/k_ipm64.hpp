@@ -11,17 +11,23 @@
 // MI355X mapping — one wavefront (64 lanes) per QP, no workgroup barriers, 2 waves per SIMD (fp64):
 //   * Newton matrix K = H + C' Sigma C in a 4 x 16-cyclic register tile: lane l = 16a + b holds
 //     K[a + 4r][b + 16c] (r = 0..15, c = 0..3) in register e = 4r + c — 64 values per lane;
-//   * LDL' elimination that also builds L^-1 in place. Step s, every row i > s and every column j != s:
-//     K[i][j] -= K[i][s] K[s][j] / d_s. For j > s this is the right-looking LDL' update; for j < s the same
-//     update accumulates the strict lower part S of the explicit inverse, X = L^-1 with X[i][j] = -S[i][j] / d_j
-//     (column s is left as it is, so the row operations on the identity need no extra storage). The 16 row
-//     multipliers K[i][s] of a lane live in its own 16-lane DPP row (column s sits in lane b = s % 16), so they
-//     arrive through row_newbcast inside v_fmac_f64_dpp at no instruction cost (dpp_rows.hpp: dpp_rowf); only the
-//     4 column multipliers K[s][j] / d_s come from LDS. One-step look-ahead: row s+1 is updated first, sent
-//     through LDS and its pivot read and inverted before the bulk of step s, so both round trips overlap the FMAs;
-//   * solves are K^-1 y = X' D^-1 X y: two matrix-vector products over the 40 registers of the strict lower part
-//     (forward: row sums reduced through LDS; backward: column sums reduced through LDS), no serial sweeps and no
-//     transpose of the factor (lab v6: 0.506 -> 0.449 ms per 4096 QPs, same iteration counts, 5e-16 vs v0);
+//   * LDL' elimination that also builds the inverses of the diagonal 16 x 16 blocks of L in place. Step s (in
+//     column chunk c0 = s / 16), every row i > s and every column j != s of the chunks c >= c0:
+//     K[i][j] -= K[i][s] K[s][j] / d_s. For j > s this is the right-looking LDL' update; for j < s (inside chunk
+//     c0) the same update accumulates, in the strict lower part S of the tile, X_cc = L_cc^-1 in the diagonal
+//     blocks (X[i][j] = -S[i][j] / d_j) and -L_c'c L_cc^-1 in the blocks below them, same encoding (column s is
+//     left as it is, so the row operations on the identity need no extra storage). The chunks c < c0 are left
+//     alone: updating them too would build the whole L^-1 (one matrix-vector product per solve half), at 400 more
+//     FMAs per factorisation at n = 60 (1920 against 1520) and a longer pivot-row exchange; this kernel is bound by
+//     VALU issue, so the fill-in outside the diagonal blocks is not formed. The 16 row multipliers K[i][s] of a lane
+//     live in its own 16-lane DPP row (column s sits in lane b = s % 16), so they arrive through row_newbcast
+//     inside v_fmac_f64_dpp at no instruction cost (dpp_rows.hpp: dpp_row); only the 4 - c0 column multipliers
+//     K[s][j] / d_s come from LDS. One-step look-ahead: row s+1 is updated first, sent through LDS and its pivot
+//     read and inverted before the bulk of step s, so both round trips overlap the FMAs;
+//   * solves are a block substitution over the four chunks, every step a 64-lane matrix-vector product over registers
+//     of the strict lower part (40 in all, each used once per half); forward: row sums reduced through LDS, the
+//     16 rows of the next block at every step and all 64 once at the end; backward: column sums reduced across the
+//     four DPP rows by permlane swaps. No serial sweeps over single pivots and no transpose of the factor;
 //   * H u is formed from the tile once (first iteration) and then carried: H du = rhs - (C' Sigma C + reg I) du from
 //     the last solve's right-hand side and the 3x3 blocks, so later iterations skip the 64-FMA product and its two
 //     LDS reductions (lab: 1.8 % per launch, iterates within 1e-14 of the direct product, same iteration counts);
@@ -78,12 +84,33 @@ namespace ipm64 {
 //     group half a bank row apart).
 constexpr int RS = 65, ZS = 20, BS = 80;
 
+// Width of the elimination's column blocks in 16-column chunks: pivot s updates the chunks c >= BW (s / 16 / BW), and
+// the solves are a substitution over 4 / BW blocks. 1 is the product; 2 (32-column blocks: 224 instead of 400 FMAs
+// saved per factorisation at n = 60, one dependent block step per solve half instead of three) and 4 (the whole L^-1,
+// no block step) are the forms it was measured against (lab/variants.txt).
+#ifndef IPM64_BW
+#define IPM64_BW 1
+#endif
+constexpr int BW = IPM64_BW;
+static_assert(BW == 1 || BW == 2 || BW == 4, "block width in chunks");
+
+// one row of the rank-1 update of pivot column B0 + 16 C0 (dpp_rows.hpp), restricted to the block width
+template <int B0, int C0, bool NOP, typename T>
+__device__ __forceinline__ void elim_row(T& k0, T& k1, T& k2, T& k3, T m0, T m1, T m2, T m3) {
+  if constexpr (BW == 1)
+    dpp_row<B0, C0, NOP, T>(k0, k1, k2, k3, m0, m1, m2, m3);
+  else if constexpr (BW == 2)
+    dpp_rowp<B0, C0, NOP, T>(k0, k1, k2, k3, m0, m1, m2, m3);
+  else
+    dpp_rowf<B0, C0, NOP, T>(k0, k1, k2, k3, m0, m1, m2, m3);
+}
+
 template <typename T>
 struct Lds {
   T v[64];          // lane-per-variable broadcast
   T w[128];         // pyramid-row broadcast
   T rowbuf[2][64];  // factorisation: row s of K as [c*16 + b]
-  T dg[64];         // pivots d_s
+  T dg[64];         // pivots d_s; 1 / d_s from the end of the factorisation on (the solves read it by column)
   T z[4 * ZS];      // solve: z permuted as [i % 4][i / 4]
   T blk[3][BS];     // Newton 3x3 block rows
   T rl[128], ru[128], itl[128], itu[128], rml[128], rmu[128];  // lane-private pyramid-row scratch
@@ -230,57 +257,129 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
   T rg_v = T(0), du_v = T(0);
   T dtl[2], dtu[2], dll[2], dlu[2];
 
-  // Solve K x = y with the eliminated tile (see the factorisation): strictly lower part S (X = L^-1 with
-  // X[i][j] = -S[i][j] / d_j), pivots d. K^-1 = X' D^-1 X, so both halves are matrix-vector products over the
-  // 40 lower registers (r >= 4c; the 16 diagonal-straddling ones were masked after the factorisation):
-  //   forward  t = D^-1 y;  z = D^-1 (y - S t)            row sums: 16 partials per lane, reduced through LDS
-  //   backward x = z - D^-1 (S' z)                         column sums: 4 partials per lane, reduced through LDS
+  // Solve K x = y with the eliminated tile (see the factorisation). Described for BW = 1 (a block is one chunk; for
+  // BW = 2 read "chunk pair", two steps): strictly lower part S in 16 x 16 blocks S_cc'
+  // over the 40 lower registers (r >= 4c; the 16 diagonal-straddling ones were masked after the factorisation),
+  // pivots d (1 / d by column in L.dg). Diagonal blocks: X_cc = L_cc^-1, X[i][j] = -S[i][j] / d_j; blocks below:
+  // -L_c'c L_cc^-1 in the same encoding. A four-block substitution, every step a 64-lane matrix-vector product:
+  //   forward, c = 0..3   yt_c = y_c - sum_{c' < c} S_cc' t_c',  t_c = D_c^-1 yt_c;   z = D^-1 (y - S t)
+  //     per-row partials stay in registers across the steps; before step c the four row-group registers of block c
+  //     (complete up to chunk c - 1) are reduced: 16 partials of 16 rows through LDS, four per lane, then across
+  //     the four DPP rows (rows_sum_dpp), which leaves yt_c by column in every lane; the full row sums for z are
+  //     reduced once at the end (16 partials per lane through LDS)
+  //   backward, c = 3..0  x_c = z_c - D_c^-1 (S_cc' z_c + sum_{c' > c} S_c'c' x_c')
+  //     column sums: one partial per DPP row, reduced by rows_sum_dpp (no LDS); x_c goes back to row order
+  //     through L.z for the steps below it
+  // Every reduction has a fixed order, the same in all lanes that hold its result.
   auto solve = [&](T& y) {
     const int ol = olane();
     const int ola = ol >> 4, olb = ol & 15;
-    L.v[ol] = y * invd_v;
+    constexpr int NBLK = 4 / BW, BR = 4 * BW;  // blocks; row-group registers per block
+    constexpr int PS = 16 * BW + 1;  // block-step partials: partial k of block row i at k * PS + i (odd stride)
+    L.v[ol] = y * invd_v;  // D^-1 y; step k turns its block k into t_k (by column, in registers)
     cbar();
-    T tc[4];
+    T p[16];
+    sfor<0, NBLK>([&](auto k_) {
+      constexpr int k = decltype(k_)::value;
+      T t[BW];
+      if constexpr (k > 0) {
+        const int wb = olb * PS + ola;  // partial olb of block row 4 rr + ola
+        sfor<0, BR>([&](auto rr_) {
+          constexpr int rr = decltype(rr_)::value;
+          L.scr[wb + 4 * rr] = p[BR * k + rr];
+        });
+        cbar();
+        const int rb = ola * PS + olb;  // partials ola, ola + 4, ola + 8, ola + 12 of block rows olb + 16 cc
+        T s[BW], t0[BW], idc[BW];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) tc[c] = L.v[olb + 16 * c];
-    cbar();
+        for (int cc = 0; cc < BW; ++cc) {
+          const int rc = rb + 16 * cc;
+          s[cc] = (L.scr[rc] + L.scr[rc + 4 * PS]) + (L.scr[rc + 8 * PS] + L.scr[rc + 12 * PS]);
+          t0[cc] = L.v[olb + 16 * (BW * k + cc)];
+          idc[cc] = L.dg[olb + 16 * (BW * k + cc)];
+        }
+        cbar();
+#pragma unroll
+        for (int cc = 0; cc < BW; ++cc) t[cc] = fma(-rows_sum_dpp(s[cc]), idc[cc], t0[cc]);
+      } else {
+#pragma unroll
+        for (int cc = 0; cc < BW; ++cc) t[cc] = L.v[olb + 16 * cc];
+        cbar();
+      }
+      // p[r] += K[r][c] t_c over the block's chunks c <= r / 4 (strict lower part)
+      auto rows = [&](auto lo_, auto hi_) {
+        sfor<decltype(lo_)::value, decltype(hi_)::value>([&](auto r_) {
+          constexpr int r = decltype(r_)::value;
+          sfor<BW * k, (r / 4 < BW * k + BW - 1 ? r / 4 : BW * k + BW - 1) + 1>([&](auto c_) {
+            constexpr int c = decltype(c_)::value;
+            p[r] = c == 0 ? K[r * 4] * t[0] : fma(K[r * 4 + c], t[c - BW * k], p[r]);
+          });
+        });
+      };
+      // the rows of block k + 1 first: they are the next step's reduction
+      rows(std::integral_constant<int, BR * k + BR>{}, std::integral_constant<int, 16>{});
+      rows(std::integral_constant<int, BR * k>{}, std::integral_constant<int, BR * k + BR>{});
+    });
     {
       const int base = olb * RS + ola;  // row 4 r + ola, partial olb
-      sfor<0, 16>([&](auto r_) {
-        constexpr int r = decltype(r_)::value;
-        T p = K[r * 4] * tc[0];
-        sfor<1, r / 4 + 1>([&](auto c_) {
-          constexpr int c = decltype(c_)::value;
-          p = fma(K[r * 4 + c], tc[c], p);
-        });
-        L.scr[base + 4 * r] = p;
-      });
+#pragma unroll
+      for (int r = 0; r < 16; ++r) L.scr[base + 4 * r] = p[r];
     }
     cbar();
     T sv = T(0);
 #pragma unroll
     for (int k = 0; k < 16; k += 2) sv += L.scr[k * RS + ol] + L.scr[(k + 1) * RS + ol];
     cbar();
-    const T z = (y - sv) * invd_v;
-    L.z[(ol & 3) * ZS + (ol >> 2)] = z;
+    L.z[(ol & 3) * ZS + (ol >> 2)] = (y - sv) * invd_v;
     cbar();
-    T zr[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zr[r] = L.z[ola * ZS + r];
-    cbar();
-    sfor<0, 4>([&](auto c_) {
-      constexpr int c = decltype(c_)::value;
-      T q = K[(4 * c) * 4 + c] * zr[4 * c];
-      sfor<4 * c + 1, 16>([&](auto r_) {
+    T zr[16];  // by row: z, block k' becomes x_k' once it is known
+    sfor_down<0, NBLK>([&](auto k_) {
+      constexpr int k = decltype(k_)::value;
+      sfor<BR * k, BR * k + BR>([&](auto r_) {
         constexpr int r = decltype(r_)::value;
-        q = fma(K[r * 4 + c], zr[r], q);
+        zr[r] = L.z[ola * ZS + r];
       });
-      L.scr[ola * 64 + c * 16 + olb] = q;
+      T zc[BW], idc[BW], qc[BW];  // z, 1 / d and the column sum by column
+#pragma unroll
+      for (int cc = 0; cc < BW; ++cc) {
+        zc[cc] = L.z[(olb & 3) * ZS + (olb >> 2) + 4 * (BW * k + cc)];
+        idc[cc] = L.dg[olb + 16 * (BW * k + cc)];
+      }
+      cbar();
+      sfor<0, BW>([&](auto cc_) {
+        constexpr int cc = decltype(cc_)::value, c = BW * k + cc;
+        T q = K[(4 * c) * 4 + c] * zr[4 * c];  // the block's own rows: z
+        sfor<4 * c + 1, BR * k + BR>([&](auto r_) {
+          constexpr int r = decltype(r_)::value;
+          q = fma(K[r * 4 + c], zr[r], q);
+        });
+        // blocks below (x), the one solved last at the end of the chain
+        sfor_down<k + 1, NBLK>([&](auto kb_) {
+          constexpr int kb = decltype(kb_)::value;
+          sfor<BR * kb, BR * kb + BR>([&](auto r_) {
+            constexpr int r = decltype(r_)::value;
+            q = fma(K[r * 4 + c], zr[r], q);
+          });
+        });
+        qc[cc] = q;
+      });
+      sfor<0, BW>([&](auto cc_) {
+        constexpr int cc = decltype(cc_)::value, c = BW * k + cc;
+        const T xc = fma(-idc[cc], rows_sum_dpp(qc[cc]), zc[cc]);  // x of column olb + 16 c, in all four DPP rows
+        if (ola == c) {
+          y = xc;
+          if constexpr (k > 0) L.z[(ol & 3) * ZS + (ol >> 2)] = xc;
+        }
+      });
+      if constexpr (k > 0) {
+        cbar();
+        sfor<BR * k, BR * k + BR>([&](auto r_) {
+          constexpr int r = decltype(r_)::value;
+          zr[r] = L.z[ola * ZS + r];
+        });
+      }
     });
     cbar();
-    const T qs = (L.scr[ol] + L.scr[64 + ol]) + (L.scr[128 + ol] + L.scr[192 + ol]);
-    cbar();
-    y = fma(-invd_v, qs, z);
   };
 
   const T* Hq = A.H + (size_t)q * ld * ld;
@@ -516,6 +615,7 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
       constexpr int c0 = s / 16, b0 = s % 16, a0 = s % 4;
       constexpr int s1 = s + 1;
       constexpr int r1 = s1 / 4, a1 = s1 % 4, c1 = s1 / 16, b1 = s1 % 16;
+      constexpr int cs1 = BW * (c1 / BW);  // first chunk pivot s + 1 updates
       if constexpr (s1 >= 60) {
         // pivots 60..63 exist only for n > 60; padding rows keep S = 0 and get d = 1
         if (!full) {
@@ -531,19 +631,24 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
       // look-ahead local row r1 (holds row s+1); for a0 < 3 it is the partial row: rows a + 4 r1 > s iff a > a0
       if constexpr (a0 < 3) {
         if (la_m > a0)
-          dpp_rowf<b0, c0, true, T>(K[r1 * 4], K[r1 * 4 + 1], K[r1 * 4 + 2], K[r1 * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
+          elim_row<b0, c0, true, T>(K[r1 * 4], K[r1 * 4 + 1], K[r1 * 4 + 2], K[r1 * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
       } else {
-        dpp_rowf<b0, c0, true, T>(K[r1 * 4], K[r1 * 4 + 1], K[r1 * 4 + 2], K[r1 * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
+        elim_row<b0, c0, true, T>(K[r1 * 4], K[r1 * 4 + 1], K[r1 * 4 + 2], K[r1 * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
       }
       cbar();
+      // row s + 1 goes round for the chunks its own step updates (c >= cs1) only
       if (la_m == a1) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) L.rowbuf[s1 & 1][c * 16 + lb_m] = K[r1 * 4 + c];
+        sfor<cs1, 4>([&](auto c_) {
+          constexpr int c = decltype(c_)::value;
+          L.rowbuf[s1 & 1][c * 16 + lb_m] = K[r1 * 4 + c];
+        });
       }
       cbar();
       T xn[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) xn[c] = L.rowbuf[s1 & 1][c * 16 + lb_m];
+      sfor<cs1, 4>([&](auto c_) {
+        constexpr int c = decltype(c_)::value;
+        xn[c] = L.rowbuf[s1 & 1][c * 16 + lb_m];
+      });
       cbar();
       const T pivn = readlane(K[r1 * 4 + c1], a1 * 16 + b1);
       T invdn = pivot_inv(pivn);
@@ -553,17 +658,17 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
         if constexpr (((r - r1 - 1) & 3) == 0) __builtin_amdgcn_sched_barrier(0);
         if constexpr (r == 15) {
           if (full)  // rows 60..63 are padding when n <= 60 (every trot / bound QP at N = 10): S stays 0 there
-            dpp_rowf<b0, c0, true, T>(K[r * 4], K[r * 4 + 1], K[r * 4 + 2], K[r * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
+            elim_row<b0, c0, true, T>(K[r * 4], K[r * 4 + 1], K[r * 4 + 2], K[r * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
         } else {
-          dpp_rowf<b0, c0, false, T>(K[r * 4], K[r * 4 + 1], K[r * 4 + 2], K[r * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
+          elim_row<b0, c0, false, T>(K[r * 4], K[r * 4 + 1], K[r * 4 + 2], K[r * 4 + 3], mm[0], mm[1], mm[2], mm[3]);
         }
       });
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
+      sfor<cs1, 4>([&](auto c_) {
+        constexpr int c = decltype(c_)::value;
         const T mv = -(xn[c] * invdn);
         mm[c] = (c == c1 && lb_m == b1) ? T(0) : mv;
-      }
+      });
       L.dg[s1] = pivn;
     });
     __builtin_amdgcn_sched_barrier(0);
@@ -574,7 +679,8 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
     IPM_STAMP(2);
 #endif
 
-    // ---- pivots -> 1/d_i (same reciprocal as the factorisation); a NaN pivot is NAN_SOL
+    // ---- pivots -> 1/d_i (same reciprocal as the factorisation); a NaN pivot is NAN_SOL. The solves' block steps
+    //      read 1/d by column, so it replaces d in L.dg until the next factorisation
     {
       const T d = L.dg[lane];
       invd_v = pivot_inv(d);
@@ -582,6 +688,8 @@ __device__ __forceinline__ void ipm64_body(const IpmArgs<T>& A, const CondenseAr
         status = CMPC_NAN_SOL;
         break;
       }
+      L.dg[lane] = invd_v;
+      cbar();
     }
     // ---- keep only the strict lower part S in the 16 registers that straddle the diagonal (r = 4c .. 4c+3)
     {

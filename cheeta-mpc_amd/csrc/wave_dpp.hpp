@@ -60,6 +60,17 @@ __device__ __forceinline__ T reduce(T x, Op op) {
 
 }  // namespace wdpp
 
+// Sum over the four 16-lane rows at equal row position (lanes b, 16 + b, 32 + b, 48 + b), the same value and the same
+// order of additions in all four: (row 0 + row 1) + (row 2 + row 3). The two swap steps of wdpp::reduce.
+template <typename T>
+__device__ __forceinline__ T rows_sum_dpp(T x) {
+  T p0, p1;
+  wdpp::swap16(x, p0, p1);
+  x = p0 + p1;
+  wdpp::swap32(x, p0, p1);
+  return p0 + p1;
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_max_dpp(T x) {
   return wdpp::reduce(x, [](T a, T b) { return a > b ? a : b; });
